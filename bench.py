@@ -3,7 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--config 3|2|tang2019|large] [--dtype f64|f32] [--gradient]
-                    [--graphs n] [--sharded] [--serial]
+                    [--graphs n] [--sharded] [--serial] [--dump-outputs DIR]
 
 A *step* is one full pass of the hot path over the batch: every pair of the
 symmetric Gram matrix of the workload is solved from device-resident graphs,
@@ -34,6 +34,11 @@ sharded over the ranks and one RCCL all-gather per step reassembles the packed
 results (`graphdot_amd.kernel.marginalized._sharded.ShardedStep`, the code
 path of `distributed_backend()`); `--sharded` takes that path on one rank too.
 
+`--dump-outputs DIR` writes what the timed path computed in its last step --
+the arrays a caller of that path receives, in the solver's arithmetic -- as
+DIR/<name>.npy (rank 0), for comparing two builds output for output: the
+inputs are seeded, so the same arguments give the same inputs.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with
 "roofline" (dominant kernel; durations from HIP events on the launch streams),
 "step_aggregate" (all launches of a step against the step time),
@@ -63,7 +68,9 @@ LDS_PEAK_TBS = {'f32': 75.0, 'f64': 150.0}  # ds_read_b32 / ds_read_b64 aggregat
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=200)
+    ap.add_argument('--steps', type=int, default=None,
+                    help='timed steps (default: 200; 5 for --config large, '
+                         '9 second launches for --config nws48)')
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', default='3',
                     choices=['2', '3', 'nws48', 'tang2019', 'large'])
@@ -125,7 +132,54 @@ def parse():
                     help='serial steps after the timed region that give the '
                          'isolated per-kernel durations (0: skip)')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as '
+                         'DIR/<name>.npy (float32/float64, at most 64 MiB '
+                         'in all; a fixed seeded sample of the pairs beyond '
+                         'that)')
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(dirname, arrays, pairs=None):
+    """`--dump-outputs`: `arrays` by name as DIR/<name>.npy, float32 or
+    float64.  If together they exceed DUMP_LIMIT_BYTES and `pairs` = (i, j)
+    is given, the arrays whose two leading axes are the matrix are written
+    at a fixed seeded sample of those pairs instead (DIR/<name>_sample.npy,
+    the pairs as DIR/sample_pairs.npy)."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            arrays[k] = v.astype(np.float64)
+
+    def size(arrays):
+        return sum(v.nbytes + NPY_HEADER_BYTES for v in arrays.values())
+    total = size(arrays)
+    if total > DUMP_LIMIT_BYTES and pairs is not None:
+        i, j = pairs
+        per_pair = sum(v[0, 0].nbytes for v in arrays.values() if v.ndim >= 2)
+        rest = sum(v.nbytes for v in arrays.values() if v.ndim < 2) \
+            + NPY_HEADER_BYTES * (len(arrays) + 1)
+        m = min(len(i), (DUMP_LIMIT_BYTES - rest) // (per_pair + 16))
+        sel = np.sort(np.random.default_rng(0).choice(len(i), size=m,
+                                                      replace=False))
+        si, sj = i[sel], j[sel]
+        arrays = {(k + '_sample' if v.ndim >= 2 else k):
+                  (v[si, sj] if v.ndim >= 2 else v)
+                  for k, v in arrays.items()}
+        arrays['sample_pairs'] = np.column_stack((si, sj)).astype(np.float64)
+        total = size(arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the limit')
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), v)
 
 
 # ---- algorithmic work of a set of jobs (SURVEY.md 8d, DESIGN.md 4) ----------
@@ -411,11 +465,17 @@ def gpr_step_line(args, world, rank, local_rank):
     barrier()
     t0 = time.perf_counter()
     for it in range(args.steps):
-        gpr.log_marginal_likelihood(theta + 1e-3 * it, eval_gradient=True)
+        last = gpr.log_marginal_likelihood(theta + 1e-3 * it,
+                                           eval_gradient=True)
         for k in parts:
             parts[k] += gpr.last_timing[k]
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            'log_marginal_likelihood': np.atleast_1d(np.asarray(
+                last[0], dtype=np.float64)),
+            'log_marginal_likelihood_gradient': last[1]})
     # (the sharded step the likelihood's gradient came from)
     step_ = getattr(backend, 'last_step', None)
     # (was the regressor handed device tensors -- device_gram -- or did it
@@ -544,6 +604,11 @@ def gpr_fit_line(args, world, rank, backend, graphs, real, dist,
     elapsed = time.perf_counter() - t0
     n_fit_evals = evals[0]
     res = gpr.optimization_result
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            'theta': np.exp(res.x),
+            'objective': np.atleast_1d(np.asarray(res.fun,
+                                                  dtype=np.float64))})
     if dist is not None and world > 1:
         dev = 'cpu' if host_collective else 'cuda'
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -626,11 +691,14 @@ def nws48_line(args):
     runtime.ensure_device()
     runtime.DeviceBuffer(1 << 20)             # context and allocator are up
     knode, kedge, q = cases.nws48_kernels()
-    rows = []
+    rows, outputs = [], {}
+    # second launches per round: round 0 (which loads the code objects) is
+    # the warm-up, the --steps timed ones are dealt over rounds 1-3
+    reps = [3] + [args.steps // 3 + (r < args.steps % 3) for r in range(3)]
     for batch in [int(b) for b in args.batch.split(',')]:
         graphs = cases.nws48_graphs(batch)
         first, second = [], []
-        for rnd in range(4):                  # (round 0 loads the code objects)
+        for rnd in range(4):
             for g in graphs:
                 for key in [k_ for k_ in g.cookie if k_ != 'rowtypes']:
                     del g.cookie[key]
@@ -639,10 +707,11 @@ def nws48_line(args):
             t0 = time.perf_counter()
             K = kernel(graphs, nodal=False)
             first.append(time.perf_counter() - t0)
-            for _ in range(3):
+            for _ in range(reps[rnd]):
                 t0 = time.perf_counter()
-                kernel(graphs, nodal=False)
+                K_last = kernel(graphs, nodal=False)
                 second.append(time.perf_counter() - t0)
+        outputs[f'K_batch{batch}'] = K_last
         plan = kernel.backend.last_plan
         n_pairs = batch * (batch + 1) // 2
         rows.append({
@@ -655,10 +724,13 @@ def nws48_line(args):
             'finite': bool(np.all(np.isfinite(K))),
             'symmetric': bool(np.array_equal(K, K.T))})
     big = rows[-1]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     return {
         'metric': 'graph-pairs/sec (Gram matrix, 2nd launch, numpy in/out)',
         'value': big['pairs'] / (1e-3 * big['second_launch_ms']),
-        'unit': 'graph-pairs/s', 'n_gpus': 1, 'steps': 9, 'warmup': 1,
+        'unit': 'graph-pairs/s', 'n_gpus': 1, 'steps': args.steps,
+        'warmup': 1,
         'ms_per_step': big['second_launch_ms'], 'higher_is_better': True,
         'scaling': 'strong', 'vs_baseline': None, 'dtype': args.dtype,
         'data': 'synthetic',
@@ -727,8 +799,13 @@ def main():
     if args.config == 'nws48':
         if args.dtype is None:
             args.dtype = 'f32'
+        if args.steps is None:
+            args.steps = 9
         emit(nws48_line(args))
         return
+    if args.steps is None:
+        # (a step of --config large is 528 pairs of ~1e5 rows each)
+        args.steps = 5 if args.config == 'large' else 200
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -752,8 +829,6 @@ def main():
         return
     if args.dtype is None:
         args.dtype = 'f64' if args.config == 3 else 'f32'
-    if args.config == 'large' and args.steps == 200:
-        args.steps = 5          # (a step is 528 pairs of ~1e5 rows each)
     sharded = world > 1 or args.sharded
 
     dist = torch = None
@@ -845,6 +920,15 @@ def main():
                          device='cpu' if host_collective else 'cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # what the timed path computed in its last step (before the isolated
+    # steps below launch the same plan again)
+    if args.dump_outputs and rank == 0:
+        vals, grads = step.download() if sharded else backend.collect(plan)
+        out = {'K': vals.reshape(n, n, order='F')}
+        if args.gradient:
+            out['dK'] = grads.reshape(n, n, nJ, order='F')[
+                :, :, np.asarray(kernel.active_theta_mask)]
+        dump_outputs(args.dump_outputs, out, (i, j))
     # per-kernel durations inside the timed region: HIP events on the stream
     # each kernel ran on (the streams share the chip: durations overlap)
     kernel_ms = np.zeros(nL)

@@ -1,7 +1,8 @@
 """Per-evaluation timings of the L-BFGS-B fit of bench.py --gpr --fit (kernel
 part, dense part, pseudo-inverse fallbacks)."""
-import sys, time, warnings
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, time, warnings
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import torch, numpy as np, cases
 from graphdot_amd.kernel.marginalized import MarginalizedGraphKernel
 from graphdot_amd.kernel.marginalized._backend_hip import HIPBackend

@@ -1,4 +1,4 @@
-"""The distributed backend (`_sharded.distributed_backend`): two and EIGHT
+"""The distributed backend (`_sharded.distributed_backend`): two and five
 ranks (one process each, sharing the single GPU of the test box through gloo)
 evaluate the kernel through the ordinary API; every rank must end up with the
 full matrix and gradient, equal to the single-process result."""
@@ -71,12 +71,14 @@ def _worker(rank, world, port, tmp):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('world', [2, 8])
+@pytest.mark.parametrize('world', [2, 5])
 def test_ranks_through_the_kernel_api(tmp_path, world):
     """Values, value + gradient, an X x Y block, `diag` and the Gaussian
-    process step end to end on `world` ranks (eight: the rank count of the
-    node BASELINE.json's configurations 4 and 5 name), every rank a process of
-    its own, against one rank."""
+    process step end to end on `world` ranks, every rank a process of its
+    own, against one rank.  Five ranks and this process are the most that
+    may hold a shared GPU at once (six); shard plans of eight ranks, the
+    rank count of the node BASELINE.json's configurations 4 and 5 name, are
+    checked on the host (test_abi_and_host_logic.py)."""
     import torch.multiprocessing as mp
     import cases
     from graphdot_amd.kernel.marginalized import MarginalizedGraphKernel
@@ -248,6 +250,39 @@ def test_bench_sharded_step_single_rank():
     assert line['config']['parallelism'] == 'pair-sharded x1'
 
 
+def test_bench_dumps_what_the_timed_path_computed(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the matrix and gradient of its
+    last timed step -- what `MarginalizedGraphKernel` returns its caller for
+    the same seeded graphs -- and `--steps` sets the number of timed
+    steps."""
+    import json
+    import subprocess
+    import cases
+    from graphdot_amd.kernel.marginalized import MarginalizedGraphKernel
+    from graphdot_amd.kernel.marginalized._backend_hip import HIPBackend
+    out = tmp_path / 'outputs'
+    r = subprocess.run(
+        [sys.executable, os.path.join(ROOT, 'bench.py'), '--graphs', '40',
+         '--steps', '3', '--warmup', '1', '--dtype', 'f64', '--gradient',
+         '--no-cpu-baseline', '--no-api', '--isolated-steps', '1',
+         '--dump-outputs', str(out)],
+        capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3
+    assert sorted(os.listdir(out)) == ['K.npy', 'dK.npy']
+    K, dK = np.load(out / 'K.npy'), np.load(out / 'dK.npy')
+    G = cases.config3_graphs(40)
+    knode, kedge, q = cases.config3_kernels()
+    k = MarginalizedGraphKernel(knode, kedge, q=q,
+                                backend=HIPBackend(real=np.float64))
+    K_api, dK_api = k(G, eval_gradient=True)
+    assert K.dtype == dK.dtype == np.float64
+    assert K.shape == K_api.shape and dK.shape == dK_api.shape
+    assert np.allclose(K, K_api, rtol=1e-10, atol=0)
+    assert np.allclose(dK, dK_api, rtol=1e-8, atol=1e-12 * np.abs(dK_api).max())
+
+
 def test_bench_spawns_its_ranks():
     """`python bench.py --gpus 2` without a launcher starts its two ranks
     itself (before anything touches the GPU in the parent) instead of running
@@ -338,7 +373,10 @@ def _alternating_worker(rank, world, port, tmp, backend_name, n_dev):
     for name, kw in (('torch', {}), ('rccl', {'collective': 'rccl'})):
         if name == 'rccl' and backend_name != 'nccl':
             continue
-        backend = distributed_backend(device=device, **kw)
+        # (shard_single_rank: a group of one rank, `_rccl_ranks` on a one-GPU
+        # node, takes the sharded path too)
+        backend = distributed_backend(device=device, shard_single_rank=True,
+                                      **kw)
         # (measured re-balancing on these small job lists too: it replaces
         # the cached plan of the evaluation it tuned -- and only that one)
         backend.rebalance_min_jobs = 1
@@ -356,7 +394,7 @@ def _alternating_worker(rank, world, port, tmp, backend_name, n_dev):
     dist.destroy_process_group()
 
 
-def _check_alternating(tmp_path, names):
+def _check_alternating(tmp_path, names, world=2):
     import cases
     from graphdot_amd.kernel.marginalized import MarginalizedGraphKernel
     from graphdot_amd.kernel.marginalized._backend_hip import HIPBackend
@@ -368,7 +406,7 @@ def _check_alternating(tmp_path, names):
     KA2, dKA = k(A, eval_gradient=True)
     KB2, dKB = k(B, eval_gradient=True)
     assert not np.allclose(KA, KB)
-    for rank in range(2):
+    for rank in range(world):
         r = np.load(tmp_path / f'alt{rank}.npz')
         for n in names:
             assert np.array_equal(r[f'{n}_KA'], KA)
@@ -397,44 +435,56 @@ def test_two_ranks_alternating_graph_sets_and_gradient_calls(tmp_path):
     _check_alternating(tmp_path, ['torch'])
 
 
-@pytest.mark.skipif(_device_count() < 2, reason='needs two GPUs')
+def _rccl_ranks():
+    """Ranks of the RCCL tests below: one per device, two where two GPUs are
+    visible.  RCCL refuses two ranks on one device, so a one-GPU node runs
+    one rank through the same "nccl" process group and code path."""
+    return min(2, _device_count())
+
+
 def test_two_ranks_on_two_devices_over_rccl(tmp_path):
-    """The multi-device branch proper (runs wherever two GPUs are visible):
-    two ranks on two devices, "nccl" process group (RCCL over xGMI), through
-    `distributed_backend()` with torch's all-gather and with
-    `collective='rccl'` (gd_comm_unique_id / gd_comm_init_rank /
-    gd_all_gather of the C ABI, per-rank gd_init(local_rank)); alternating
-    graph sets, values and gradients; bit-equal to one rank."""
+    """The multi-device branch proper: one rank per device (two ranks on two
+    devices wherever two GPUs are visible, `_rccl_ranks`), "nccl" process
+    group (RCCL over xGMI), through `distributed_backend()` with torch's
+    all-gather and with `collective='rccl'` (gd_comm_unique_id /
+    gd_comm_init_rank / gd_all_gather of the C ABI, per-rank
+    gd_init(local_rank)); alternating graph sets, values and gradients;
+    bit-equal to one rank."""
     import torch.multiprocessing as mp
+    world = _rccl_ranks()
     port = 29100 + os.getpid() % 200
-    mp.spawn(_alternating_worker, args=(2, port, str(tmp_path), 'nccl', 2),
-             nprocs=2, join=True)
-    _check_alternating(tmp_path, ['torch', 'rccl'])
+    mp.spawn(_alternating_worker,
+             args=(world, port, str(tmp_path), 'nccl', world),
+             nprocs=world, join=True)
+    _check_alternating(tmp_path, ['torch', 'rccl'], world)
 
 
-@pytest.mark.skipif(_device_count() < 2, reason='needs two GPUs')
 def test_bench_two_gpus_sharded():
-    """`bench.py --gpus 2` on two real devices: RCCL, two ranks, the
-    reassembled matrix against the oracle; and the GPR step on two ranks."""
+    """`bench.py --gpus N` with one rank per device (N = 2 wherever two GPUs
+    are visible, `_rccl_ranks`; on one GPU `--sharded`, the same path on a
+    group of one): RCCL, the reassembled matrix against the oracle; and the
+    GPR step on the same ranks."""
     import json
     import subprocess
+    n = _rccl_ranks()
     env = {k: v for k, v in os.environ.items()
            if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT',
                         'MASTER_ADDR')}
     for extra in (['--no-cpu-baseline'], ['--gradient', '--no-cpu-baseline'],
                   ['--gpr']):
         r = subprocess.run(
-            [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
+            [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n),
+             *(['--sharded'] if n == 1 else []),
              '--graphs', '200', '--steps', '3', '--warmup', '1', *extra],
             capture_output=True, text=True, env=env, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
-        assert line['n_gpus'] == 2
+        assert line['n_gpus'] == n
         if '--gpr' in extra:
             assert line['collective'] == 'nccl(RCCL)'
             assert line['device_resident_kernel_matrix']
         else:
             chk = line['sharded_check']
-            assert chk['collective'] == 'nccl(RCCL)' and chk['ranks'] == 2
+            assert chk['collective'] == 'nccl(RCCL)' and chk['ranks'] == n
             # (double arithmetic at the reference's stopping rule, 1e-8 N)
             assert chk['max_rel_diff_vs_oracle'] < 1e-6

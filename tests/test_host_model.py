@@ -607,26 +607,132 @@ def test_composite_kernels_of_one_shape_share_a_class_not_their_state():
     assert np.allclose(list(flatten(a.theta)), ta)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/graphdot'),
-                    reason='needs the reference checkout (build container)')
+def _seam_calls(k, G):
+    """The calls of tests/golden/make_golden_dropin.py, in its order."""
+    k(G)
+    k(G, eval_gradient=True)
+    k(G, nodal=True)
+    k(G, nodal=True, eval_gradient=True)
+    k(G[:1], G[1:])
+    k(G, lmin=1)
+    k.diag(G)
+    k.diag(G, eval_gradient=True)
+    k.diag(G, nodal=True)
+    k.diag(G, nodal='block')
+
+
+def _struct_values(buf):
+    if buf is None:
+        return []
+    if buf.dtype.names is None:
+        return [float(v) for v in np.ravel(buf)]
+    return [v for name in buf.dtype.names for v in _struct_values(buf[name])]
+
+
+def _host_half_of_prepare(backend, graphs, node_kernel, edge_kernel, p, jobs,
+                          traits):
+    """Everything of `HIPBackend.prepare` that needs no device: graph packing,
+    solver variants and launch order, code generation, hipcc JIT, the
+    kernel-argument values.  Returns those values by field."""
+    from graphdot_amd.hip import jit
+    from graphdot_amd.kernel.marginalized._backend_hip import pack_theta
+    ngrad = traits.eval_gradient is True and traits.nodal is True
+    if traits.eval_gradient is True and traits.nodal == 'block':
+        traits = traits._replace(eval_gradient=False)
+    dgraphs, ek, C, fields = backend._graphs_and_kernels(
+        graphs, node_kernel, edge_kernel, traits, None, ngrad)
+    arena = backend._host_arena(dgraphs, fields)
+    tab_bytes = 0 if ngrad else backend._table_bytes(arena)
+    gtab = backend._global_tables(arena) and not ngrad
+    _, used, order_all, launches = backend._partition(
+        dgraphs, jobs, C, tab_bytes, gtab, oc_only=ngrad)
+    assert sorted(order_all.tolist()) == list(range(len(jobs)))
+    assert sum(L['count'] for L in launches) == len(jobs)
+    sources = backend._sources(used, node_kernel, ek, p, dgraphs, C,
+                               traits.nodal is not False, tab_bytes > 0,
+                               gtab, ngrad)
+    paths = jit.compile_many(list(sources.values()), backend.hipcc_extra)
+    assert len(paths) == len(sources) and all(map(os.path.getsize, paths))
+    return {field: _struct_values(pack_theta(obj, backend.real)[1])
+            for field, obj in (('node_kernel', node_kernel),
+                               ('edge_kernel', ek), ('p_start', p))}
+
+
 def test_reference_kernel_object_drives_the_hip_backend():
-    """The seam regression test: the REFERENCE's MarginalizedGraphKernel
-    (`graphdot/kernel/marginalized/_kernel.py:224-242,363-381`) constructs the
-    arguments of `HIPBackend.__call__` from its own Graph / microkernel
-    objects, for value, gradient, nodal, X x Y, lmin and the three `diag`
-    modes; everything of `prepare` that needs no device runs on them
-    (tests/golden/check_dropin.py, in a process of its own: the numpy /
-    pycuda shims the reference's import needs must not leak into this one).
-    Skipped where /root/reference does not exist (the GPU box)."""
-    import subprocess
-    import sys
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                          'golden', 'check_dropin.py')
-    r = subprocess.run([sys.executable, script], capture_output=True,
-                       text=True, timeout=1500)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert 'drop-in seam ok' in r.stdout
-    assert r.stdout.count('10 backend calls') == 4
+    """The seam regression test: the arguments the REFERENCE's
+    MarginalizedGraphKernel (`graphdot/kernel/marginalized/_kernel.py:224-242,
+    363-381`) constructs for its backend from its own Graph / microkernel
+    objects -- value, gradient, nodal, X x Y, lmin and the three `diag` modes
+    on the four case families of its test oracle -- as recorded with a
+    HIPBackend in its place (tests/golden/dropin_seam.json, written by
+    make_golden_dropin.py).  This package's kernel object hands its backend
+    the same arguments for the same calls; everything of `prepare` that
+    needs no device runs on the recorded ones; and the kernel arguments
+    packed from this package's microkernels equal those packed from the
+    reference's."""
+    from _fixtures import kernel_from_repr
+    from graphdot_amd.kernel.marginalized._backend_hip import HIPBackend
+    job_t = np.dtype([('i', np.uint32), ('j', np.uint32)])
+    seam = load('dropin_seam.json')
+    mlgk_cases = load('mlgk_cases.json')
+    ours = []
+
+    class Recording(HIPBackend):
+        def __call__(self, graphs, node_kernel, edge_kernel, p, q, eps, ftol,
+                     gtol, jobs, starts, gramian, gradient, nX, nY, nJ,
+                     traits, timer):
+            ours.append(dict(
+                n_graphs=len(graphs), q=q, eps=eps, ftol=ftol, gtol=gtol,
+                jobs=np.array(jobs), starts=np.array(starts),
+                gramian=[gramian.dtype.str, gramian.ndim, gramian.size],
+                gradient=None if gradient is None else
+                [gradient.dtype.str, gradient.ndim, gradient.size],
+                nX=nX, nY=nY, nJ=nJ, traits=traits))
+            gramian[:] = 1.0                     # (no launch: placeholders)
+            if gradient is not None:
+                gradient[:] = 0.0
+
+    backend = Recording()
+    assert sorted(seam) == sorted(
+        k_ for k_, v in mlgk_cases.items() if isinstance(v, dict))
+    for name, rec in seam.items():
+        case = mlgk_cases[name]
+        G = graphs_from(case['graphs'])
+        knode = kernel_from_repr(case['knode'])
+        kedge = kernel_from_repr(case['kedge'])
+        k = MarginalizedGraphKernel(knode, kedge, q=rec['q'], backend=backend)
+        del ours[:]
+        _seam_calls(k, G)
+        assert len(ours) == len(rec['calls']) == 10
+        for mine, ref in zip(ours, rec['calls']):
+            at = (name, ref['call'])
+            traits = k.trait_t(**ref['traits'])
+            jobs = np.column_stack((ref['jobs_i'], ref['jobs_j'])).astype(
+                np.uint32).ravel().view(job_t)
+            starts = np.array(ref['starts'], dtype=ref['starts_dtype'])
+            nX, nY, nJ = ref['nX'], ref['nY'], ref['nJ']
+            # -- the contract of the seam (reference _kernel.py:172-242) ----
+            assert [tuple(d) for d in ref['jobs_dtype']] == job_t.descr, at
+            assert starts.dtype == np.uint32, at
+            assert ref['gramian'] == ['<f4', 1, nX * nY], at
+            if traits.eval_gradient is True:
+                assert ref['gradient'] == ['<f4', 1, nX * nY * nJ], at
+            else:
+                assert ref['gradient'] is None, at
+            assert max(jobs['i'].max(), jobs['j'].max()) < ref['n_graphs'], at
+            # -- this package's caller: the same arguments ------------------
+            assert mine['traits'] == traits, at
+            assert np.array_equal(mine['jobs'], jobs), at
+            assert np.array_equal(mine['starts'], starts), at
+            assert (mine['nX'], mine['nY'], mine['nJ']) == (nX, nY, nJ), at
+            assert mine['gramian'] == ref['gramian'], at
+            assert mine['gradient'] == ref['gradient'], at
+            for key in ('n_graphs', 'q', 'eps', 'ftol', 'gtol'):
+                assert mine[key] == ref[key], (at, key)
+            # -- host-only half of HIPBackend.prepare on the recorded call --
+            theta = _host_half_of_prepare(backend, G, knode, kedge, k.p, jobs,
+                                          traits)
+            assert theta == ref['theta'], at
 
 
 @pytest.mark.parametrize('weighted', [False, True])
