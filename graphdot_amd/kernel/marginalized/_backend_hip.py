@@ -660,6 +660,16 @@ class HIPBackend(Backend):
                 max(int(nbytes * 1.25), 256))
         return buf
 
+    def detach_outputs(self, plan):
+        """Hand the output buffers of `plan` over to whoever holds the
+        plan: the pool forgets them, so that the next evaluation on this
+        backend writes into buffers of its own instead of over these
+        (`MarginalizedGraphKernel.device_cross_gram` / `device_diag`)."""
+        for name in ('gramian', 'gradient'):
+            buf = plan.buffers.get(name)
+            if buf is not None and self._pool.get(name) is buf:
+                del self._pool[name]
+
     # -- graphs ---------------------------------------------------------------
     def _register_graph(self, graph):
         key = (self.uuid.int, np.dtype(self.real).str)   # (an int hashes in C)

@@ -362,6 +362,92 @@ class MarginalizedGraphKernel:
                                  (nx, nx, self.n_dims), real, owner=plan)
         return K, dK
 
+    def _device_backend(self, what):
+        backend = self.backend
+        if not hasattr(backend, 'prepare'):
+            raise TypeError(f'{what} needs the HIP backend')
+        if getattr(backend, 'shards_over_ranks', lambda: False)():
+            raise TypeError(f'{what}: no pair-sharded evaluation')
+        return backend
+
+    def _device_result(self, backend, graphs, jobs, starts, nX, nY, shape,
+                       traits):
+        """One evaluation left on the device, in output buffers that belong
+        to the returned views alone (see `device_cross_gram`)."""
+        from ...hip.runtime import DeviceArray, DeviceBuffer
+        real = np.dtype(backend.real)
+        n_out = int(np.prod(shape))
+        if n_out == 0:
+            # (nothing to solve: empty views instead of a zero-size launch)
+            owner = DeviceBuffer(256)
+            K = DeviceArray.fortran(owner.ptr, shape, real, owner=owner)
+            if not traits.eval_gradient:
+                return K
+            return K, DeviceArray.fortran(owner.ptr, (*shape, self.n_dims),
+                                          real, owner=owner)
+        plan = backend.prepare(
+            graphs, self.node_kernel, self.edge_kernel, self.p, self.q,
+            self.eps, self.ftol, self.gtol, jobs, starts, nX, nY,
+            self.n_dims, traits)
+        backend.detach_outputs(plan)
+        backend.launch(plan)
+        backend.synchronize()
+        K = DeviceArray.fortran(plan.buffers['gramian'].ptr, shape, real,
+                                owner=plan)
+        if not traits.eval_gradient:
+            return K
+        dK = DeviceArray.fortran(plan.buffers['gradient'].ptr,
+                                 (*shape, self.n_dims), real, owner=plan)
+        return K, dK
+
+    def device_cross_gram(self, X, Y, eval_gradient=False, lmin=0):
+        """`__call__(X, Y)` -- the len(X) x len(Y) matrix and, with
+        `eval_gradient`, its (len(X), len(Y), n_dims) gradient -- left in
+        device memory: views (`graphdot_amd.hip.runtime.DeviceArray`) in the
+        backend's arithmetic, column-major, with every `n_dims` column
+        (`active_theta_mask` is the caller's to apply).
+
+        Unlike `device_gram`'s, these views own their buffers: a later
+        evaluation on the same backend does not overwrite them, and the
+        memory is released when the last view (or a torch tensor that adopted
+        it) is gone.  TypeError if the backend is not HIP, or shards pairs
+        over ranks."""
+        backend = self._device_backend('device_cross_gram')
+        all_graphs = list(it.chain(X, Y))
+        pred = Graph.has_unified_types(all_graphs)
+        if pred is not True:
+            raise _type_error(
+                pred, 'If the attributes match in name but differ in type, '
+                'try `Graph.unify_datatype` as an automatic fix.')
+        nx, ny = len(X), len(Y)
+        starts = np.zeros(nx + ny + 1, dtype=np.uint32)
+        starts[:nx] = np.arange(nx)
+        starts[nx:] = np.arange(ny + 1)
+        jobs = self._pairwise_jobs(nx, ny) if nx and ny else None
+        traits = self.traits(lmin=lmin, eval_gradient=eval_gradient)
+        return self._device_result(backend, np.concatenate((X, Y)), jobs,
+                                   starts, nx, ny, (nx, ny), traits)
+
+    def device_diag(self, X, eval_gradient=False, lmin=0):
+        """`diag(X, eval_gradient, active_theta_only=False)` -- the graph
+        self-similarities (len(X),) and their (len(X), n_dims) gradient --
+        left in device memory, in buffers of their own (see
+        `device_cross_gram`)."""
+        backend = self._device_backend('device_diag')
+        pred = Graph.has_unified_types(X)
+        if pred is not True:
+            raise _type_error(
+                pred, 'If the attribute names do match, then try to unify '
+                'data types automatically with `Graph.unify_datatype`.')
+        n = len(X)
+        i = np.arange(n, dtype=np.uint32)
+        jobs = np.column_stack((i, i)).ravel().view(_job_t)
+        traits = self.traits(diagonal=True, lmin=lmin,
+                             eval_gradient=eval_gradient)
+        return self._device_result(backend, X, jobs,
+                                   np.arange(n + 1, dtype=np.uint32), n, 1,
+                                   (n,), traits)
+
     # ------------------------------------------------------------------ diag
     def diag(self, X, eval_gradient=False, nodal=False, lmin=0,
              active_theta_only=True, timing=False):

@@ -1,10 +1,12 @@
 """Gaussian process regression on the kernel protocol; mirrors
-``graphdot.model.gaussian_process`` of the reference for the GPR class."""
+``graphdot.model.gaussian_process`` of the reference for the exact and the
+Nystrom low-rank regressor."""
 try:      # torch's HIP runtime must be initialised before libgdhip's
     import torch as _torch   # (graphdot_amd.hip.runtime, _let_torch_initialise_first)
     _torch.cuda.is_available()
 except ImportError:          # pragma: no cover
     pass
 from .gpr import GaussianProcessRegressor
+from .nystrom import LowRankApproximateGPR
 
-__all__ = ['GaussianProcessRegressor']
+__all__ = ['GaussianProcessRegressor', 'LowRankApproximateGPR']
