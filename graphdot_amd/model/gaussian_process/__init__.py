@@ -1,6 +1,6 @@
 """Gaussian process regression on the kernel protocol; mirrors
 ``graphdot.model.gaussian_process`` of the reference for the exact and the
-Nystrom low-rank regressor."""
+Nystrom low-rank regressor and the outlier detector."""
 try:      # torch's HIP runtime must be initialised before libgdhip's
     import torch as _torch   # (graphdot_amd.hip.runtime, _let_torch_initialise_first)
     _torch.cuda.is_available()
@@ -8,5 +8,7 @@ except ImportError:          # pragma: no cover
     pass
 from .gpr import GaussianProcessRegressor
 from .nystrom import LowRankApproximateGPR
+from .outlier_detector import GPROutlierDetector
 
-__all__ = ['GaussianProcessRegressor', 'LowRankApproximateGPR']
+__all__ = ['GaussianProcessRegressor', 'LowRankApproximateGPR',
+           'GPROutlierDetector']
