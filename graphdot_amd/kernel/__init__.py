@@ -1,2 +1,10 @@
 """Graph kernels: the marginalized graph kernel (the hot path), the kernel
-transformers of ``fix`` and the ready-made molecular kernel."""
+transformers of ``fix``, the ready-made molecular kernel and kernels over a
+distance (`KernelOverMetric`)."""
+from .molecular import Tang2019MolecularKernel
+from ._kernel_over_metric import KernelOverMetric
+from .marginalized import MarginalizedGraphKernel
+
+__all__ = [
+    'Tang2019MolecularKernel', 'KernelOverMetric', 'MarginalizedGraphKernel'
+]

@@ -2533,6 +2533,35 @@ void ${name}(params_t prm) {
         does (_backend.cu:383); default: the unperturbed solution.  Returns (distance
         [nX nY], hotspot int32 [nX nY], gradient [nX nY nJ] or None), flat
         column-major like the other outputs."""
+        plan = self._maximin_launch(
+            graphs, node_kernel, edge_kernel, p, q, eps, ftol, gtol, jobs, nX,
+            nY, nJ, traits, timer, reference_compat)
+        dist, g = self.collect(plan)
+        hot = np.empty(plan.n_out, dtype=np.int32)
+        plan.buffers['hotspot'].download(hot)
+        return dist, hot, g
+
+    def maximin_distance_device(self, graphs, node_kernel, edge_kernel, p, q,
+                                eps, ftol, gtol, jobs, nX, nY, nJ, traits,
+                                timer=None, reference_compat=False):
+        """`maximin_distance` whose results stay on the device: the same
+        launches, then the pair plan's output buffers are handed over
+        (`detach_outputs`) instead of collected -- ``plan.buffers['gramian']``
+        holds the distances, ``plan.buffers['gradient']`` the gradient (nJ
+        columns), flat column-major; no hotspots are downloaded.  Returns the
+        plan once its launches are complete."""
+        plan = self._maximin_launch(
+            graphs, node_kernel, edge_kernel, p, q, eps, ftol, gtol, jobs, nX,
+            nY, nJ, traits, timer, reference_compat, detach=True)
+        self.synchronize()
+        return plan
+
+    def _maximin_launch(self, graphs, node_kernel, edge_kernel, p, q, eps,
+                        ftol, gtol, jobs, nX, nY, nJ, traits, timer=None,
+                        reference_compat=False, detach=False):
+        """The launches of `maximin_distance` (both enqueued, nothing
+        collected); returns the pair plan.  `detach`: its output buffers
+        leave the pool (`detach_outputs`)."""
         grad = traits.eval_gradient is True
         n = len(graphs)
         sizes = np.array([len(g.nodes) for g in graphs], dtype=np.uint32)
@@ -2579,13 +2608,12 @@ void ${name}(params_t prm) {
                          diag_grad=b_dgrad.ptr if grad else 0,
                          node_starts=b_ns.ptr, ld=total,
                          reference_compat=bool(reference_compat)))
+        if detach:
+            self.detach_outputs(plan)
         if grad:
             plan.buffers['gradient'].zero()
         self.launch(plan)
-        dist, g = self.collect(plan)
-        hot = np.empty(plan.n_out, dtype=np.int32)
-        plan.buffers['hotspot'].download(hot)
-        return dist, hot, g
+        return plan
 
     # -- the reference's backend call ---------------------------------------------------
     def __call__(self, graphs, node_kernel, edge_kernel, p, q, eps, ftol,

@@ -128,18 +128,13 @@ class MaxiMin(MarginalizedGraphKernel):
             out.append(grad.astype(self.element_dtype))
         return out[0] if len(out) == 1 else tuple(out)
 
-    def _fused(self, X, Y, eval_gradient, lmin, return_hotspot):
-        """The device-fused evaluation, or None if the backend / the graphs
-        do not offer it."""
-        backend = self.backend
-        if not hasattr(backend, 'maximin_distance') or \
-                getattr(backend, 'shards_over_ranks', lambda: False)():
-            return None
+    def _maximin_args(self, X, Y, eval_gradient, lmin):
+        """The arguments of `HIPBackend.maximin_distance` for X (and Y), or
+        None if the graph types are not unified (the composition raises)."""
         from ...graph import Graph
-        from ...kernel.marginalized._backend_hip import NotOwnerComputes
         graphs = list(X) if Y is None else list(X) + list(Y)
         if Graph.has_unified_types(graphs) is not True:
-            return None            # let the composition raise the type error
+            return None
         nx, ny = len(X), len(X if Y is None else Y)
         if Y is None:
             i, j = np.triu_indices(nx)
@@ -151,11 +146,31 @@ class MaxiMin(MarginalizedGraphKernel):
             np.uint32).ravel().view(job_t)
         traits = self.traits(symmetric=Y is None, nodal=False, lmin=lmin,
                              eval_gradient=eval_gradient)
+        return (graphs, self.node_kernel, self.edge_kernel, self.p, self.q,
+                self.eps, self.ftol, self.gtol, jobs, nx, ny, self.n_dims,
+                traits)
+
+    def _fused_backend(self):
+        backend = self.backend
+        if not hasattr(backend, 'maximin_distance') or \
+                getattr(backend, 'shards_over_ranks', lambda: False)():
+            return None
+        return backend
+
+    def _fused(self, X, Y, eval_gradient, lmin, return_hotspot):
+        """The device-fused evaluation, or None if the backend / the graphs
+        do not offer it."""
+        backend = self._fused_backend()
+        if backend is None:
+            return None
+        from ...kernel.marginalized._backend_hip import NotOwnerComputes
+        args = self._maximin_args(X, Y, eval_gradient, lmin)
+        if args is None:
+            return None            # let the composition raise the type error
+        nx, ny = args[9], args[10]
         try:
             d, hot, g = backend.maximin_distance(
-                graphs, self.node_kernel, self.edge_kernel, self.p, self.q,
-                self.eps, self.ftol, self.gtol, jobs, nx, ny, self.n_dims,
-                traits, reference_compat=self.reference_compat)
+                *args, reference_compat=self.reference_compat)
         except NotOwnerComputes:
             return None
         out = [d.reshape(nx, ny, order='F').astype(self.element_dtype)]
@@ -169,3 +184,39 @@ class MaxiMin(MarginalizedGraphKernel):
                 self.element_dtype))
         return out[0] if len(out) == 1 else tuple(out)
 
+    def device_distance(self, X, Y=None, eval_gradient=False, lmin=0):
+        """The distance matrix (len(X), len(Y or X)) and, with
+        `eval_gradient`, its (len(X), len(Y or X), n_dims) gradient over
+        every hyperparameter (`active_theta_mask` is the caller's to apply),
+        left in device memory: views (`graphdot_amd.hip.runtime.DeviceArray`)
+        in the backend's arithmetic, column-major, that own their buffers
+        like `device_cross_gram`'s.  The same launches as `__call__`, so the
+        same values.  TypeError where the fused evaluation does not apply: a
+        backend that is not HIP, pairs sharded over ranks, graphs the
+        owner-computes solvers do not cover, attribute types not unified."""
+        from ...hip.runtime import DeviceArray
+        from ...kernel.marginalized._backend_hip import NotOwnerComputes
+        backend = self._fused_backend()
+        if backend is None or not hasattr(backend, 'maximin_distance_device'):
+            raise TypeError('device_distance needs the HIP backend, '
+                            'unsharded')
+        args = self._maximin_args(X, Y, eval_gradient, lmin)
+        if args is None:
+            raise TypeError('device_distance: graph attribute types differ')
+        nx, ny = args[9], args[10]
+        if nx == 0 or ny == 0:
+            raise TypeError('device_distance: no pairs')
+        try:
+            plan = backend.maximin_distance_device(
+                *args, reference_compat=self.reference_compat)
+        except NotOwnerComputes:
+            raise TypeError('device_distance: graphs beyond the '
+                            'owner-computes solvers') from None
+        real = np.dtype(backend.real)
+        D = DeviceArray.fortran(plan.buffers['gramian'].ptr, (nx, ny), real,
+                                owner=plan)
+        if not eval_gradient:
+            return D
+        dD = DeviceArray.fortran(plan.buffers['gradient'].ptr,
+                                 (nx, ny, self.n_dims), real, owner=plan)
+        return D, dD
