@@ -181,6 +181,9 @@ struct params_fd_t {
 // the non-negative float distances (order independent: deterministic), the
 // n1 x n2 nodal block never leaves the CU.  k1, k2 (and their Jacobians) are
 // the nodal self-similarities of the two graphs from a `diag` launch.
+// MAXIMIN == 2 is the M3 flavour (graphdot.experimental.metric.m3): double
+// distances sqrt(max(2 - 2 k12 / sqrt(k1 k2), 0)) without offset, the same
+// Hausdorff reduction on their 64-bit patterns, no hotspot, no gradient.
 // Workgroup sums with ONE barrier each: the per-wave partials go to one of two
 // scratch halves, and consecutive reductions alternate between them -- the
 // barrier of reduction k + 1 (other half) is behind every wave's reads of
@@ -234,7 +237,7 @@ template<class K> struct packed_edge<K, std::void_t<typename K::packed_edge_t>> 
     using type = typename K::packed_edge_t;
 };
 
-template<class real, int S, int R, int W, int C, bool NODAL, int DMAX, bool TAB, bool NGRAD, bool MAXIMIN, class LAY, class Graph, class NodeK, class EdgeK, class PStart>
+template<class real, int S, int R, int W, int C, bool NODAL, int DMAX, bool TAB, bool NGRAD, int MAXIMIN, class LAY, class Graph, class NodeK, class EdgeK, class PStart>
 struct oc_solver {
     constexpr static bool STATIC = LAY::is_static;
     // (Round 6, measured and dropped: static layouts of SEVERAL waves per pair
@@ -264,6 +267,7 @@ struct oc_solver {
     constexpr static int SA = S > 0 ? S : 1;    // slot array extent
     constexpr static int FLY_U = 4;             // terms per trip of the inner loop (2 / 4 / 8 measured: 5.06 / 4.95 / 4.33 M pairs/s before the dense product, which walks blocks of four)
     static_assert(!MAXIMIN || (NODAL && C == 1), "the maximin epilogue works on the nodal solution of a value solve");
+    static_assert(MAXIMIN != 2 || (!NGRAD && sizeof(real) == 8), "the M3 epilogue: double values, no gradient");
     using P = params_t<real, Graph, NodeK, EdgeK, PStart>;
     using PF = std::conditional_t<NGRAD, params_fd_t<real, Graph, NodeK, EdgeK, PStart>, P>;
     __device__ static __forceinline__ P const &common(P const &p) { return p; }
@@ -477,7 +481,7 @@ struct oc_solver {
         real red[2][2 * W];     // two halves: see alternating_reduce
         int tab_off[NTAB];      // sorted-row offset of rectangle d1 * NC + d2
         int tab_cls[64];        // [0..NC) start1, [16..) cnt2, [32..) start2
-        unsigned mm_cell[4];    // MAXIMIN: distance bits, hotspot, mirrored hotspot
+        unsigned mm_cell[4];    // MAXIMIN: distance bits, hotspot, mirrored hotspot; M3: [0..1] distance bits
     };
 
     __device__ static __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -1670,7 +1674,7 @@ struct oc_solver {
             [[maybe_unused]] real mm_pp = 0, mm_corr = 0, mm_xlast = 0;
             [[maybe_unused]] unsigned mm_n1 = 0, mm_n2 = 0;   // node offsets of the graphs
             [[maybe_unused]] unsigned mm_hot = 0;             // flat index of the hotspot
-            if constexpr (MAXIMIN) {
+            if constexpr (MAXIMIN == 1) {
                 // row / column minima in the region of p (dead between the solve
                 // and the re-solves; n1 + n2 <= n1 (n2 | 1) + 1 <= u_capacity words
                 // for every n1, n2 >= 1 -- the row-sum region holds NR words in
@@ -1752,6 +1756,79 @@ struct oc_solver {
                     }
                 }
                 job_sync<W>();   // the region of p is published to again below
+            }
+
+            // ---- M3 distance of the pair (MAXIMIN == 2) -----------------------
+            //   K = k12 / sqrt(k1 k2),  d = sqrt(max(2 - 2 K, 0)),
+            //   D = max(max_i1 min_i2 d, max_i2 min_i1 d)
+            // in double, written to the graph-level output.  The minima and
+            // their maximum are LDS atomics on the 64-bit patterns of the
+            // non-negative double distances (order independent:
+            // deterministic).  A graph with itself (job.i == job.j) takes
+            // k1 = k2 from the diagonal of its own solution, so that K(i, i)
+            // is k12 / sqrt(k12 k12) and d(G, G) is round-off, not the CG
+            // tolerance.  The square roots are Newton-refined (graphdot::rsqrt):
+            // the bare v_rsq_f64 that fast-math makes of 1 / sqrt is good to
+            // ~1e-8 only.
+            if constexpr (MAXIMIN == 2) {
+                // 8-byte cells in the region of p (u_capacity reals, dead
+                // between the solve and the next pair): row minima [n1],
+                // column minima [n2], and for a self pair the nodal diagonal
+                // [n1].  n1 + n2 <= n1 (n2 | 1) + 1 <= u_capacity for every
+                // n1, n2 >= 1; a self pair needs 3 n <= n (n | 1) + 1, true
+                // from n = 2 on, and u_capacity >= 4 covers n = 1.
+                using u64 = unsigned long long;
+                static_assert(__builtin_offsetof(lds_t, mm_cell) % 8 == 0, "64-bit cell");
+                u64 *const dmin1 = reinterpret_cast<u64 *>(lp);
+                u64 *const dmin2 = dmin1 + n1;
+                real *const sdiag = reinterpret_cast<real *>(dmin2 + n2);
+                u64 *const cell = reinterpret_cast<u64 *>(lds.mm_cell);
+                const bool self = job.i == job.j;
+                const unsigned NS1 = prm.node_starts[job.i], NS2 = prm.node_starts[job.j];
+                job_sync<W>();
+                for (int i = tid; i < n1 + n2; i += T) dmin1[i] = 0x7FF0000000000000ull;   // +inf
+                if (tid == 0) cell[0] = 0ull;
+                real k12v[R];
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+                    const int pos = row_pos(k, wv, lane);
+                    const bool ok = pos < N;
+                    const unsigned rm = rowmap[ok ? pos : 0];
+                    const int i1 = (int)(rm >> 16), i2 = (int)(rm & 0xFFFFu);
+                    const node_t v1 = g1.node[i1], v2 = g2.node[i2];
+                    real xi = x[0][k];
+                    if (flags & F_LMIN1) xi -= kappa_v(i1, i2, v1, v2) * bscale;
+                    k12v[k] = xi * (real(prm.p_start(v1)) * real(prm.p_start(v2)));
+                    if (self && ok && i1 == i2) sdiag[i1] = k12v[k];
+                }
+                job_sync<W>();
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+                    const int pos = row_pos(k, wv, lane);
+                    const bool ok = pos < N;
+                    const unsigned rm = rowmap[ok ? pos : 0];
+                    const int i1 = (int)(rm >> 16), i2 = (int)(rm & 0xFFFFu);
+                    if (ok) {
+                        const real k1 = self ? sdiag[i1] : prm.diag[NS1 + g1.perm[i1]];
+                        const real k2 = self ? sdiag[i2] : prm.diag[NS2 + g2.perm[i2]];
+                        const real kn = k12v[k] * graphdot::rsqrt(k1 * k2);
+                        const real v = real(2) - real(2) * kn;
+                        const real d = v > real(0) ? v * graphdot::rsqrt(v) : real(0);
+                        const u64 bits = (u64)__double_as_longlong(d);
+                        __hip_atomic_fetch_min(dmin1 + i1, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_min(dmin2 + i2, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+                job_sync<W>();
+                for (int i = tid; i < n1 + n2; i += T)
+                    __hip_atomic_fetch_max(cell, dmin1[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                job_sync<W>();
+                if (tid == 0) {
+                    const real D = __longlong_as_double((long long)cell[0]);
+                    prm.gramian[(size_t)I1 + (size_t)prm.nX * I2] = D;
+                    if (mirror) prm.gramian[(size_t)I2 + (size_t)prm.nX * I1] = D;
+                }
+                job_sync<W>();   // the region of p and the cell: the next pair
             }
             if (!NODAL || !(flags & F_NODAL)) {
                 job_sync<W>();   // (the loop may have left through either half)

@@ -3,9 +3,9 @@
 Only the input surface the hot path needs is provided (scope):
 ``Graph(nodes, edges, title)``, ``from_networkx``, ``unify_datatype``,
 ``has_unified_types``, ``permute``, ``copy``, ``cookie``,
-``adjacency_matrix``/``laplacian`` and ``to_networkx``.  Semantics follow the
-reference's ``graphdot/graph/__init__.py:40-357``; the chemistry importers
-(ase / pymatgen / rdkit) are out of scope.
+``adjacency_matrix``/``laplacian``, ``to_networkx`` and ``from_ase``.
+Semantics follow the reference's ``graphdot/graph/__init__.py:40-357``; the
+pymatgen / rdkit importers are out of scope.
 """
 import copy as cp
 import itertools as it
@@ -16,6 +16,7 @@ from ..util.cookie import VolatileCookie, IdentityCache
 
 _UNIFIED = IdentityCache()
 from ._from_networkx import _from_networkx, _to_networkx
+from ._from_ase import _from_ase
 
 __all__ = ['Graph']
 
@@ -194,11 +195,20 @@ class Graph:
     def to_networkx(self):
         return _to_networkx(self)
 
-    # chemistry importers of the reference: out of scope
     @classmethod
-    def from_ase(cls, *args, **kwargs):
-        raise NotImplementedError(
-            'from_ase is outside the MI355X hot-path scope; build a NetworkX '
-            'graph and use Graph.from_networkx instead.')
+    def from_ase(cls, atoms, adjacency='default', use_charge=False,
+                 use_pbc=True):
+        """Molecular graph of atoms in 3D space (an ASE ``Atoms`` or any
+        object with the same few methods): see `_from_ase`."""
+        return _from_ase(cls, atoms, adjacency=adjacency,
+                         use_charge=use_charge, use_pbc=use_pbc)
 
-    from_pymatgen = from_rdkit = from_smiles = from_ase
+    # chemistry importers that need rdkit / pymatgen: out of scope (DESIGN.md)
+    @classmethod
+    def from_rdkit(cls, *args, **kwargs):
+        raise NotImplementedError(
+            'from_rdkit / from_smiles / from_pymatgen need packages this '
+            'project does not depend on; use Graph.from_ase or '
+            'Graph.from_networkx instead.')
+
+    from_pymatgen = from_smiles = from_rdkit

@@ -874,7 +874,8 @@ struct ${name}_t : ${name}_theta_t {
             return f'mgk_{f}_oc{v.D}_W{v.W}_S{v.S}_R{v.R}_C{C}' + \
                 ('_L' + 'x'.join(map(str, v.L)) if v.L else '') + \
                 ('_nodal' if nodal else '') + ('_tab' if tab else '') + \
-                ('_ngrad' if ngrad else '') + ('_maximin' if maximin else '')
+                ('_ngrad' if ngrad else '') + (
+                    '_m3' if maximin == 2 else '_maximin' if maximin else '')
         return f'mgk_{f}_W{v.W}_S{v.S}_R{v.R}_C{C}' + \
             ('_nodal' if nodal else '') + ('_tab' if tab else '')
 
@@ -1067,7 +1068,7 @@ void ${name}(${params} prm) {
             name=self.kernel_name(v, C, nodal, tab, ngrad, maximin),
             dlds='true' if self.diagonals_in_lds(v, C, nodal or ngrad
                                                  or bool(maximin)) else 'false',
-            maximin='true' if maximin else 'false',
+            maximin='2' if maximin == 2 else 'true' if maximin else 'false',
             layout=('graphdot::mgk::seg_layout<%s>' % ', '.join(map(str, v.L))
                     if v.L else 'graphdot::mgk::dynamic_layout'),
             S=v.S, R=v.R, W=v.W, C=C, D=v.D if v.S else 1,
@@ -1980,7 +1981,7 @@ void ${name}(params_t prm) {
                     tab=gtab if isinstance(v, OCVariant)
                     else (tab and v not in (GENERAL, TABLES, STREAM, MFMA)),
                     weighted=dgraphs[0].weighted, ngrad=ngrad,
-                    maximin=maximin and isinstance(v, OCVariant))
+                    maximin=maximin if isinstance(v, OCVariant) else False)
             out[k] = self._source_cache[key]
         return out
 
@@ -2107,8 +2108,10 @@ void ${name}(params_t prm) {
         node_kernel_in, edge_kernel_in = node_kernel, edge_kernel
         dgraphs, edge_kernel, C, fields = self._graphs_and_kernels(
             graphs, node_kernel, edge_kernel, traits, timer, ngrad)
+        # epilogue flavour: 0 none, 1 maximin, 2 M3 (mgk_oc.h MAXIMIN)
+        flavour = 0 if maximin is None else (2 if maximin.get('m3') else 1)
         lay = self._layout(dgraphs, jobs, starts, C, fields, timer, ngrad,
-                           maximin is not None, merge_map,
+                           flavour, merge_map,
                            nodal=traits.nodal is not False,
                            mfma=self._label_blind(edge_kernel_in))
         tab = lay.tab_bytes > 0
@@ -2120,7 +2123,7 @@ void ${name}(params_t prm) {
         # renders, hashes and looks up nothing
         mkey = (self._code_signature(node_kernel, edge_kernel, p, dgraphs, C,
                                      nodal, tab, lay.gtab, ngrad,
-                                     maximin is not None), tuple(lay.used),
+                                     flavour), tuple(lay.used),
                 tuple(self.hipcc_extra), self.tables,
                 None if self.occupancy is None
                 else tuple(sorted(self.occupancy.items())))
@@ -2128,7 +2131,7 @@ void ${name}(params_t prm) {
         if hit is None:
             sources = self._sources(lay.used, node_kernel, edge_kernel, p,
                                     dgraphs, C, nodal, tab, lay.gtab, ngrad,
-                                    maximin is not None)
+                                    flavour)
             toc('code generation')
             tic('JIT')
             missing = [s for s in sources.values()
@@ -2182,7 +2185,7 @@ void ${name}(params_t prm) {
                 else tab and L['variant'] not in (GENERAL, STREAM, MFMA)
             L['fn'] = fn = L['module'].function(
                 self.kernel_name(L['variant'], C, nodal, L['tab'], ngrad,
-                                 maximin is not None))
+                                 flavour))
             if L['variant'] == STREAM:
                 # few pairs: several workgroups per pair, a cooperative
                 # launch (mgk_stream.h).  M = what the chip holds at once over
@@ -2556,12 +2559,47 @@ void ${name}(params_t prm) {
         self.synchronize()
         return plan
 
+    # -- M3 graph distance, fused ------------------------------------------------------
+    def m3_distance(self, graphs, node_kernel, edge_kernel, p, q, eps, ftol,
+                    gtol, jobs, nX, nY, nJ, traits, timer=None):
+        """M3 distances (graphdot_amd.experimental.metric.m3) of the graph
+        pairs in `jobs`, fused like `maximin_distance`: a `diag` launch leaves
+        the nodal self-similarities on the device, the pair launch reduces
+        them with the pair's nodal solution in LDS (mgk_oc.h, MAXIMIN == 2,
+        kernels named ``*_m3``).  Double backends only, no gradient;
+        owner-computes solvers only (NotOwnerComputes otherwise).  Returns the
+        distances [nX nY], flat column-major."""
+        plan = self.m3_distance_device(graphs, node_kernel, edge_kernel, p, q,
+                                       eps, ftol, gtol, jobs, nX, nY, nJ,
+                                       traits, timer, detach=False)
+        dist, _ = self.collect(plan)
+        return dist
+
+    def m3_distance_device(self, graphs, node_kernel, edge_kernel, p, q, eps,
+                           ftol, gtol, jobs, nX, nY, nJ, traits, timer=None,
+                           detach=True):
+        """`m3_distance` whose result stays on the device: returns the pair
+        plan once its launches are complete, ``plan.buffers['gramian']``
+        holding the distances (handed over with `detach_outputs` unless
+        `detach` is False)."""
+        if np.dtype(self.real) != np.float64:
+            raise TypeError('M3 distances need a double backend '
+                            '(HIPBackend(real=np.float64))')
+        if traits.eval_gradient is True:
+            raise NotImplementedError('M3 has no gradient')
+        plan = self._maximin_launch(
+            graphs, node_kernel, edge_kernel, p, q, eps, ftol, gtol, jobs, nX,
+            nY, nJ, traits, timer, detach=detach, m3=True)
+        self.synchronize()
+        return plan
+
     def _maximin_launch(self, graphs, node_kernel, edge_kernel, p, q, eps,
                         ftol, gtol, jobs, nX, nY, nJ, traits, timer=None,
-                        reference_compat=False, detach=False):
+                        reference_compat=False, detach=False, m3=False):
         """The launches of `maximin_distance` (both enqueued, nothing
         collected); returns the pair plan.  `detach`: its output buffers
-        leave the pool (`detach_outputs`)."""
+        leave the pool (`detach_outputs`).  `m3`: the M3 epilogue instead
+        (`m3_distance`)."""
         grad = traits.eval_gradient is True
         n = len(graphs)
         sizes = np.array([len(g.nodes) for g in graphs], dtype=np.uint32)
@@ -2607,7 +2645,8 @@ void ${name}(params_t prm) {
             maximin=dict(diag=b_diag.ptr,
                          diag_grad=b_dgrad.ptr if grad else 0,
                          node_starts=b_ns.ptr, ld=total,
-                         reference_compat=bool(reference_compat)))
+                         reference_compat=bool(reference_compat),
+                         m3=bool(m3)))
         if detach:
             self.detach_outputs(plan)
         if grad:

@@ -2,7 +2,10 @@
 """Dump the gfx950 ISA of one solver variant built for the bench workload
 (QM7-like TensorProduct kernels) -- for instruction-count work on the CG loop.
 
-    python scripts/dump_isa.py W S R [C] [--f64] [--oc=D] [--layout=16x4x4x1] [--tab|--tab=2] [--config2|--tang] > out.s
+    python scripts/dump_isa.py W S R [C] [--f64] [--oc=D] [--layout=16x4x4x1] [--tab|--tab=2] [--config2|--tang] [--maximin|--m3] > out.s
+
+--maximin / --m3: the fused epilogue flavours of the owner-computes solvers
+(nodal value solve, direct microkernel evaluation; --m3 needs --f64).
 """
 import os
 import subprocess
@@ -42,10 +45,16 @@ lay = [a.split('=')[1] for a in sys.argv if a.startswith('--layout=')]
 variant = OCVariant(W, S, R, oc[0]) if oc else Variant(W, S, R)
 if lay:       # --layout=16x4x4x1 (W S R are then ignored)
     variant = OCStatic(*map(int, lay[0].split('x')))
-src = backend.render_source(kn, ke2, k.p, node_t, edge_t, [variant], C,
-                            tab=2 if '--tab=2' in sys.argv else '--tab' in sys.argv,
-                            weighted=dgs[0].weighted)
-path = f'/tmp/_dump_isa_{W}_{S}_{R}_{C}_{int(real is np.float64)}.hip'
+flavour = 2 if '--m3' in sys.argv else 1 if '--maximin' in sys.argv else 0
+if flavour:
+    src = backend.render_source(kn, ke2, k.p, node_t, edge_t, [variant], C,
+                                nodal=True, weighted=dgs[0].weighted,
+                                maximin=flavour)
+else:
+    src = backend.render_source(kn, ke2, k.p, node_t, edge_t, [variant], C,
+                                tab=2 if '--tab=2' in sys.argv else '--tab' in sys.argv,
+                                weighted=dgs[0].weighted)
+path = f'/tmp/_dump_isa_{W}_{S}_{R}_{C}_{int(real is np.float64)}_{flavour}.hip'
 open(path, 'w').write(src)
 flags = [f for f in jit.BASE_FLAGS if f != '--genco'] + \
     os.environ.get('GD_HIPCC_EXTRA', '').split()
