@@ -9,6 +9,7 @@ except ImportError:          # pragma: no cover
 from .gpr import GaussianProcessRegressor
 from .nystrom import LowRankApproximateGPR
 from .outlier_detector import GPROutlierDetector
+from ._device_posterior import DevicePosterior
 
 __all__ = ['GaussianProcessRegressor', 'LowRankApproximateGPR',
-           'GPROutlierDetector']
+           'GPROutlierDetector', 'DevicePosterior']

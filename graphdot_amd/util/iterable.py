@@ -1,8 +1,9 @@
 """Tree <-> flat-sequence helpers used by the hyperparameter plumbing.
 
 API-compatible with the reference's ``graphdot/util/iterable.py:5-37``
-(``flatten``, ``fold_like``, ``replace``).
+(``flatten``, ``fold_like``, ``replace``, ``argmax``).
 """
+from functools import reduce
 
 
 def flatten(tree):
@@ -46,3 +47,11 @@ def replace(iterable, old, new):
             yield new
         else:
             yield item
+
+
+def argmax(iterable, less):
+    """The largest item under the strict order ``less(a, b)``; of several
+    equally large ones the first; None for an empty iterable."""
+    items = iter(iterable)
+    return reduce(lambda best, item: item if less(best, item) else best,
+                  items, next(items, None))
