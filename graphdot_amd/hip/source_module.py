@@ -1,0 +1,117 @@
+"""Host side shared by the fused dense kernels (the ``.hip`` files next to the
+models that use them): `SourceModule` compiles one HIP source into the JIT
+cache of `jit` and loads it once per process; `STATIC` lists the sources that
+are files of the package, each with its flags, for their host modules and for
+``__graft_entry__.build()``.  Below them, the few lines every torch-facing
+launch repeats.  Nothing here imports torch (or a package that does) at module
+level: `build()` compiles through this module before ``libgdhip.so`` is used.
+"""
+import os
+import struct
+import threading
+
+from . import jit, runtime
+
+_PACKAGE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+#: IEEE arithmetic: none of jit.BASE_FLAGS' fast-math for these kernels
+DENSE_FLAGS = ('-fno-fast-math',)
+_lock = threading.Lock()
+_loaded = {}        # jit cache key -> runtime.Module (one per code object)
+
+
+class SourceModule:
+    """One HIP translation unit, given as the path of a file or as text."""
+
+    def __init__(self, path=None, source=None, flags=DENSE_FLAGS):
+        assert (path is None) != (source is None)
+        self.path = path
+        self._source = source
+        self.flags = tuple(flags)
+        self._key = None
+
+    @property
+    def source(self):
+        if self._source is None:
+            with open(self.path) as f:
+                self._source = f.read()
+        return self._source
+
+    @property
+    def key(self):
+        if self._key is None:
+            self._key = jit.cache_key(self.source, self.flags)
+        return self._key
+
+    def precompile(self):
+        """Compile into the JIT cache (hipcc, no device needed); the path of
+        the code object."""
+        return jit.compile_source(self.source, self.flags)
+
+    @property
+    def module(self):
+        """The loaded `runtime.Module`: one per process and code object,
+        whichever `SourceModule` of that source asks first.  (Kept in this
+        module, not in the object: a kernel that holds its map can still be
+        copied or pickled.)"""
+        mod = _loaded.get(self.key)
+        if mod is None:
+            with _lock:
+                mod = _loaded.get(self.key)
+                if mod is None:
+                    mod = _loaded[self.key] = runtime.Module(
+                        jit.load_image(self.precompile()))
+        return mod
+
+    def function(self, name):
+        """Kernel `name` (looked up on first use; HIPError if the code object
+        has none of that name)."""
+        return self.module.function(name)
+
+    def launch(self, name, grid, block, fmt, *args, stream=None):
+        """Launch kernel `name` with the arguments `args` packed as the
+        struct format `fmt` (native alignment, as the kernel's parameters)."""
+        runtime.launch(self.function(name), grid, block,
+                       struct.pack('@' + fmt, *args), stream=stream)
+
+
+#: the sources that are files of the package, relative to it
+STATIC_SOURCES = (
+    'model/gaussian_process/potrf.hip',
+    'model/active_learning/select.hip',
+    'model/gaussian_process/lowrank.hip',
+    'model/gaussian_field/field.hip',
+    'model/gaussian_process/outlier.hip',
+    'model/gaussian_process/posterior.hip',
+)
+#: file name -> SourceModule
+STATIC = {os.path.basename(p): SourceModule(os.path.join(_PACKAGE, p))
+          for p in STATIC_SOURCES}
+
+#: planes / candidates per register chunk (the template parameter KC of the
+#: kernels that keep a chunk of accumulators in registers)
+CHUNKS = (1, 2, 4, 8, 16)
+
+
+def chunk(n):
+    """The chunk size for `n` planes: the smallest of CHUNKS that holds them,
+    the largest when none does."""
+    return next(k for k in CHUNKS if k >= min(max(n, 1), CHUNKS[-1]))
+
+
+def suffix(dtype):
+    """'f32' / 'f64', as the kernels' names spell a torch dtype."""
+    import torch
+    if dtype == torch.float32:
+        return 'f32'
+    if dtype == torch.float64:
+        return 'f64'
+    raise TypeError(f'float32 or float64 expected, got {dtype}')
+
+
+def current_stream(device):
+    """Raw handle of torch's current stream on `device` (None: the null
+    stream).  Launches go there to be ordered against the torch operations
+    around them -- and torch's caching allocator then hands a workspace freed
+    after a launch out again only behind that launch."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream or None

@@ -11,17 +11,13 @@ so the cache key, depends only on the expression, the distance symbol and the
 hyperparameter names, and an optimiser's steps never compile again."""
 import functools
 import os
-import struct
-import threading
 import numpy as np
 import sympy
+from ..hip.source_module import SourceModule, current_stream, suffix
 
 _TEMPLATE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                          'kernel_over_metric.hip')
-_FLAGS = ('-fno-fast-math',)
 _BLOCK = 256
-_lock = threading.Lock()
-_modules = {}          # cache key -> {kernel name: function}
 
 
 def _print(expr, symbols):
@@ -68,38 +64,12 @@ def device_map(expr, x, names):
     return DeviceMap(expr, x, names)
 
 
-class DeviceMap:
+class DeviceMap(SourceModule):
     """The compiled map of one formula."""
 
     def __init__(self, expr, x, names):
+        super().__init__(source=generate(expr, x, names))
         self.n_hyper = len(names)
-        self.source = generate(expr, x, names)
-
-    @property
-    def key(self):
-        from ..hip import jit
-        return jit.cache_key(self.source, _FLAGS)
-
-    def precompile(self):
-        """Compile into the JIT cache (hipcc, no device needed)."""
-        from ..hip import jit
-        return jit.compile_source(self.source, _FLAGS)
-
-    def _load(self):
-        key = self.key
-        with _lock:
-            fn = _modules.get(key)
-            if fn is None:
-                from ..hip import jit, runtime
-                mod = runtime.Module(jit.load_image(self.precompile()))
-                fn = {f'kom_{m}_{a}_{b}': None
-                      for m in ('value', 'dense', 'lazy')
-                      for a in ('f32', 'f64') for b in ('f32', 'f64')}
-                for name in list(fn):
-                    fn[name] = mod.function(name)
-                fn['module'] = mod
-                _modules[key] = fn
-        return fn
 
     def __call__(self, D, h, P=None, planes=(), form='value'):
         """Map the distance matrix D (an (nr, nc) float32 / float64 CUDA
@@ -110,7 +80,6 @@ class DeviceMap:
         and S = df/dx.  Every output float64, column-major, enqueued on
         torch's current stream."""
         import torch
-        from ..hip import runtime
         if D.dim() != 2 or not D.is_cuda:
             raise TypeError('D: a 2-D CUDA tensor expected')
         h = np.asarray(h, dtype=np.float64).ravel()
@@ -145,30 +114,24 @@ class DeviceMap:
             elif form != 'value':
                 raise ValueError(f'unknown form {form!r}')
             if nr and nc:
-                tp = P.dtype if np_ else D.dtype
-                sfx = {torch.float32: 'f32', torch.float64: 'f64'}
-                if D.dtype not in sfx or tp not in sfx:
-                    raise TypeError('float32 or float64 expected')
+                name = (f'kom_{form}_{suffix(D.dtype)}_'
+                        f'{suffix(P.dtype if np_ else D.dtype)}')
                 pk = torch.from_numpy(planes).to(dev) if np_ else None
                 gx = -(-nr // _BLOCK)
                 if gx * nc >= 2**31:
                     raise ValueError(f'{nr} x {nc}: too many workgroups')
-                args = struct.pack(
-                    '@Qqqqqq' + 'Qqqq' + 'Qq' + 'QQQ',
+                self.launch(
+                    name, gx * nc, _BLOCK,
+                    'Qqqqqq' + 'Qqqq' + 'Qq' + 'QQQ'
+                    + f'{max(self.n_hyper, 1)}d',
                     D.data_ptr(), D.stride(0), D.stride(1), nr, nc, gx,
                     P.data_ptr() if np_ else 0,
                     *(P.stride()[:3] if np_ else (0, 0, 0)),
                     pk.data_ptr() if np_ else 0, np_,
                     K.data_ptr(), G.data_ptr() if G is not None else 0,
-                    S.data_ptr() if S is not None else 0)
-                args += struct.pack(f'@{max(self.n_hyper, 1)}d',
-                                    *(h if self.n_hyper else [0.0]))
-                name = f'kom_{form}_{sfx[D.dtype]}_{sfx[tp]}'
-                stream = torch.cuda.current_stream().cuda_stream or None
-                runtime.launch(self._load()[name], gx * nc, _BLOCK, args,
-                               stream=stream)
-                # (pk is freed into torch's cache on this stream: handed out
-                # again only behind this launch)
+                    S.data_ptr() if S is not None else 0,
+                    *(h if self.n_hyper else [0.0]),
+                    stream=current_stream(dev))
         if form == 'value':
             return K
         if form == 'dense':

@@ -5,45 +5,14 @@ torch's *current* stream of the matrix's device, in stream order, two or
 three per pick; the pivot index never leaves the device, and the only host
 synchronisation is the one download at the end (the picks and the status
 word)."""
-import os
-import struct
-import threading
+from ...hip.source_module import STATIC, current_stream, suffix
 
-_SOURCE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                       'select.hip')
-_FLAGS = ('-fno-fast-math',)
+_module = STATIC['select.hip']
 _BLOCK = 256
 _WAVES = _BLOCK // 64
-_lock = threading.Lock()
-_kernels = None
 
 #: status words of select.hip
 ST_OK, ST_DM_RESIDUAL, ST_VM_RESIDUAL, ST_NO_CANDIDATE = 0, 1, 2, 3
-
-
-def source():
-    with open(_SOURCE) as f:
-        return f.read()
-
-
-def precompile():
-    """Compile into the JIT cache (hipcc, no device needed)."""
-    from ...hip import jit
-    return jit.compile_source(source(), _FLAGS)
-
-
-def _load():
-    global _kernels
-    with _lock:
-        if _kernels is None:
-            from ...hip import jit, runtime
-            mod = runtime.Module(jit.load_image(precompile()))
-            _kernels = {name: mod.function(name) for name in (
-                'al_colreduce_f32', 'al_colreduce_f64',
-                'al_dm_direction_f32', 'al_dm_direction_f64',
-                'al_vm_column_f32', 'al_vm_column_f64', 'al_update_argmax')}
-            _kernels['module'] = mod
-    return _kernels
 
 
 def column_major(K):
@@ -68,17 +37,15 @@ def select(K, n, method, alpha=0.0, tol=0.0):
     array, status word)."""
     import numpy as np
     import torch
-    from ...hip import runtime
     K = column_major(K)
     N = K.shape[0]
     assert 1 <= n <= N
-    sfx = 'f32' if K.dtype == torch.float32 else 'f64'
-    fn = _load()
+    sfx = suffix(K.dtype)
     G = -(-N // _BLOCK)
     dev = K.device
     f64 = dict(dtype=torch.float64, device=dev)
+    stream = current_stream(dev)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream or None
         # [status, direction counter, update counter, pad, picks[n]]
         # (picks not reached stay -1: the caller counts the valid ones)
         iw = torch.full((4 + n,), -1, dtype=torch.int32, device=dev)
@@ -96,8 +63,7 @@ def select(K, n, method, alpha=0.0, tol=0.0):
     p_V, p_W = V.data_ptr(), W.data_ptr()
 
     def launch(name, grid, fmt, *args):
-        runtime.launch(fn[name], grid, _BLOCK, struct.pack('@' + fmt, *args),
-                       stream=stream)
+        _module.launch(name, grid, _BLOCK, fmt, *args, stream=stream)
 
     def update(s, op, nxt):
         launch('al_update_argmax', G, 'iiiiQQQQQiQQQQQQ', N, s, op, nxt,

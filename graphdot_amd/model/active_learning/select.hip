@@ -22,11 +22,8 @@
 // argmax keeps the largest criterion and, among equal values, the smallest
 // index; a NaN never wins.  A pivot whose residual is not above `tol` times
 // its own size sets the status word and every later launch returns at once.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "dense_reduce.h"
 
-#define BLOCK 256
-#define WAVE 64
 #define CHUNK 1024   // coefficients staged in LDS per pass
 
 enum { ST_OK = 0, ST_DM_RESIDUAL = 1, ST_VM_RESIDUAL = 2, ST_NO_CANDIDATE = 3 };
@@ -42,11 +39,6 @@ __device__ __forceinline__ int ld_agent(const int *p) {
 }
 __device__ __forceinline__ void st_agent(int *p, int v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
 }
 
 // sum over the block (every thread gets it); `red` holds BLOCK / WAVE doubles

@@ -17,17 +17,7 @@
 // over the four waves and gy column sets, KC planes per chunk in registers,
 // a shape-only grid and a fixed-order second-stage reduction, no atomics:
 // repeated calls give the same bits.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#define BLOCK 256
-#define WAVE 64
-#define NWAVE (BLOCK / WAVE)
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
+#include "dense_reduce.h"
 
 // d and w of one element, in the order of operations of the host path
 __device__ __forceinline__ void field_weight(double k, double kr, double kc,
@@ -231,17 +221,5 @@ extern "C" __global__ __launch_bounds__(BLOCK) void
 gf_reduce(const double *__restrict__ partial, int64_t nblk,
           double *__restrict__ out)
 {
-    __shared__ double red[NWAVE];
-    const double *p = partial + (int64_t)blockIdx.x * nblk;
-    double s = 0.0;
-    for (int64_t b = threadIdx.x; b < nblk; b += BLOCK) s += p[b];
-    s = wave_sum(s);
-    const int lane = threadIdx.x % WAVE, wid = threadIdx.x / WAVE;
-    if (lane == 0) red[wid] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < NWAVE; ++w) t += red[w];
-        out[blockIdx.x] = t;
-    }
+    reduce_partials(partial, nblk, out);
 }

@@ -4,54 +4,21 @@ arithmetic: no fast-math) and runs them on torch's *current* stream of the
 planes' device, in stream order with the torch operations around them.  Two
 launches per call (the pass over the planes, the fixed-order reduction of
 its per-workgroup sums) and no host synchronisation."""
-import os
-import struct
-import threading
 import numpy as np
+from ...hip.source_module import STATIC, chunk, current_stream, suffix
 
-_SOURCE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                       'lowrank.hip')
-_FLAGS = ('-fno-fast-math',)
+_module = STATIC['lowrank.hip']
 _BLOCK = 256
 _ROWS = 64           # rows per workgroup (one per lane)
 _WAVES = 4           # columns per workgroup and step (one per wave)
-_CHUNKS = (1, 2, 4, 8, 16)     # planes per register chunk (template KC)
 _TARGET_BLOCKS = 2048          # workgroups to aim for (256 CUs x 8)
-_lock = threading.Lock()
-_kernels = None
-
-
-def source():
-    with open(_SOURCE) as f:
-        return f.read()
-
-
-def precompile():
-    """Compile into the JIT cache (hipcc, no device needed)."""
-    from ...hip import jit
-    return jit.compile_source(source(), _FLAGS)
-
-
-def _load():
-    global _kernels
-    with _lock:
-        if _kernels is None:
-            from ...hip import jit, runtime
-            mod = runtime.Module(jit.load_image(precompile()))
-            _kernels = {f'lr_contract_{t}_k{kc}': None
-                        for t in ('f32', 'f64') for kc in _CHUNKS}
-            for name in list(_kernels):
-                _kernels[name] = mod.function(name)
-            _kernels['lr_reduce'] = mod.function('lr_reduce')
-            _kernels['module'] = mod
-    return _kernels
 
 
 def grid(Nr, M, nt):
     """(chunk size KC, row tiles gx, column sets gy, chunks gz; the launch
     has gx gy gz workgroups): a function of the shapes alone, so that the
     order of every sum is the same on every call."""
-    kc = next(k for k in _CHUNKS if k >= min(nt, _CHUNKS[-1]))
+    kc = chunk(nt)
     gz = -(-nt // kc)
     gx = -(-Nr // _ROWS)
     gy = max(1, min(-(-M // _WAVES), -(-_TARGET_BLOCKS // (gx * gz))))
@@ -81,7 +48,6 @@ def contract(P, W, rows=None):
     N here).  Returns a float64 tensor of n sums on P's device, enqueued on
     torch's current stream."""
     import torch
-    from ...hip import runtime
     _check_planes(P)
     N, M, nt = P.shape
     dev = P.device
@@ -107,24 +73,17 @@ def contract(P, W, rows=None):
             return out
         if rows is not None:
             rows_t = torch.from_numpy(rows).to(dev, non_blocking=False)
-        stream = torch.cuda.current_stream().cuda_stream or None
+        stream = current_stream(dev)
         kc, gx, gy, gz = grid(Nr, M, nt)
         nblk = gx * gy
         partial = torch.empty(nt * nblk, dtype=torch.float64, device=dev)
-        fn = _load()
-        sfx = 'f32' if P.dtype == torch.float32 else 'f64'
-        runtime.launch(
-            fn[f'lr_contract_{sfx}_k{kc}'], gx * gy * gz, _BLOCK,
-            struct.pack('@QqqiQqQqiiQ', P.data_ptr(), N, M, nt, W.data_ptr(),
-                        ldw, rows_t.data_ptr() if rows_t is not None else 0,
-                        Nr, gx, gy, partial.data_ptr()),
-            stream=stream)
-        runtime.launch(fn['lr_reduce'], nt, _BLOCK,
-                       struct.pack('@QqQ', partial.data_ptr(), nblk,
-                                   out.data_ptr()),
-                       stream=stream)
-        # (the workspaces are freed into torch's cache on this stream: the
-        # allocator hands them out again only behind these launches)
+        _module.launch(
+            f'lr_contract_{suffix(P.dtype)}_k{kc}', gx * gy * gz, _BLOCK,
+            'QqqiQqQqiiQ', P.data_ptr(), N, M, nt, W.data_ptr(), ldw,
+            rows_t.data_ptr() if rows_t is not None else 0, Nr, gx, gy,
+            partial.data_ptr(), stream=stream)
+        _module.launch('lr_reduce', nt, _BLOCK, 'QqQ', partial.data_ptr(),
+                       nblk, out.data_ptr(), stream=stream)
     return out
 
 

@@ -4,53 +4,21 @@ IEEE arithmetic: no fast-math) and runs them on torch's *current* stream of
 the matrices' device, in stream order with the torch operations around them.
 Three launches per call (the rows of the inverse, the pass over the gradient
 planes, the fixed-order reduction) and no host synchronisation."""
-import os
-import struct
-import threading
 import numpy as np
+from ...hip.source_module import STATIC, chunk, current_stream, suffix
 
-_SOURCE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                       'outlier.hip')
-_FLAGS = ('-fno-fast-math',)
+_module = STATIC['outlier.hip']
 _BLOCK = 256
 _WAVES = 4          # rows per workgroup of od_rows (one per wave)
 _TILE = 64          # rows and columns per tile of od_planes
 _SUB = 4            # workgroups per tile (TILE / SUB columns each)
-_CHUNKS = (1, 2, 4, 8, 16)     # planes per register chunk (template KC)
-_lock = threading.Lock()
-_kernels = None
-
-
-def source():
-    with open(_SOURCE) as f:
-        return f.read()
-
-
-def precompile():
-    """Compile into the JIT cache (hipcc, no device needed)."""
-    from ...hip import jit
-    return jit.compile_source(source(), _FLAGS)
-
-
-def _load():
-    global _kernels
-    with _lock:
-        if _kernels is None:
-            from ...hip import jit, runtime
-            mod = runtime.Module(jit.load_image(precompile()))
-            names = ['od_rows', 'od_reduce']
-            names += [f'od_planes_{t}_k{kc}' for t in ('f32', 'f64')
-                      for kc in _CHUNKS]
-            _kernels = {name: mod.function(name) for name in names}
-            _kernels['module'] = mod
-    return _kernels
 
 
 def grid(n, nt):
     """(chunk size KC, tiles on and above the diagonal, chunks): od_planes
     runs tiles x SUB x chunks workgroups.  A function of the shapes alone,
     so that the order of every sum is the same on every call."""
-    kc = next(k for k in _CHUNKS if k >= min(max(nt, 1), _CHUNKS[-1]))
+    kc = chunk(nt)
     nb = -(-n // _TILE)
     return kc, nb * (nb + 1) // 2, max(1, -(-nt // kc))
 
@@ -88,7 +56,6 @@ def epilogue(Kinv, Ks, y, sigma2, P=None, planes=()):
     `device_gram` hands them over column-major).  planes: indices into the
     m planes (`active_theta_mask`)."""
     import torch
-    from ...hip import runtime
     n = Kinv.shape[0]
     if not Kinv.is_cuda:
         raise TypeError('epilogue runs on CUDA tensors; see epilogue_torch')
@@ -117,14 +84,11 @@ def epilogue(Kinv, Ks, y, sigma2, P=None, planes=()):
         out = torch.zeros(3 + nt + n, dtype=torch.float64, device=dev)
         if n == 0:
             return out
-        stream = torch.cuda.current_stream().cuda_stream or None
-        fn = _load()
+        stream = current_stream(dev)
         rows = torch.empty(5 * n, dtype=torch.float64, device=dev)
-        runtime.launch(fn['od_rows'], -(-n // _WAVES), _BLOCK,
-                       struct.pack('@QQqQQQ', Kinv.data_ptr(), Ks.data_ptr(),
-                                   n, y.data_ptr(), sigma2.data_ptr(),
-                                   rows.data_ptr()),
-                       stream=stream)
+        _module.launch('od_rows', -(-n // _WAVES), _BLOCK, 'QQqQQQ',
+                       Kinv.data_ptr(), Ks.data_ptr(), n, y.data_ptr(),
+                       sigma2.data_ptr(), rows.data_ptr(), stream=stream)
         kc, ntiles, gz = grid(n, nt)
         nblk = ntiles * _SUB
         partial = torch.empty(max(nt, 1) * nblk, dtype=torch.float64,
@@ -132,20 +96,14 @@ def epilogue(Kinv, Ks, y, sigma2, P=None, planes=()):
         if nt:
             pidx = torch.from_numpy(planes).to(dev)
             s_lane, s_col, s_k = plane_strides(P)
-            sfx = 'f32' if P.dtype == torch.float32 else 'f64'
-            runtime.launch(
-                fn[f'od_planes_{sfx}_k{kc}'], nblk * gz, _BLOCK,
-                struct.pack('@QqqqqQiQQqQ', P.data_ptr(), n, s_lane, s_col,
-                            s_k, pidx.data_ptr(), nt, Kinv.data_ptr(),
-                            rows.data_ptr(), ntiles, partial.data_ptr()),
-                stream=stream)
-        runtime.launch(fn['od_reduce'], 3 + nt + -(-n // _BLOCK), _BLOCK,
-                       struct.pack('@QqQqiQ', rows.data_ptr(), n,
-                                   partial.data_ptr(), nblk, nt,
-                                   out.data_ptr()),
-                       stream=stream)
-        # (the workspaces are freed into torch's cache on this stream: the
-        # allocator hands them out again only behind these launches)
+            _module.launch(
+                f'od_planes_{suffix(P.dtype)}_k{kc}', nblk * gz, _BLOCK,
+                'QqqqqQiQQqQ', P.data_ptr(), n, s_lane, s_col, s_k,
+                pidx.data_ptr(), nt, Kinv.data_ptr(), rows.data_ptr(), ntiles,
+                partial.data_ptr(), stream=stream)
+        _module.launch('od_reduce', 3 + nt + -(-n // _BLOCK), _BLOCK,
+                       'QqQqiQ', rows.data_ptr(), n, partial.data_ptr(), nblk,
+                       nt, out.data_ptr(), stream=stream)
     return out
 
 

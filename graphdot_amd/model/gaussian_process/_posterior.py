@@ -5,50 +5,24 @@ fast-math) and runs them on torch's *current* stream of the inverse's device,
 in stream order with the torch operations around them.  Two launches per call
 (the rows of the inverse, the fixed-order reduction with the epilogue) and no
 host synchronisation."""
-import os
-import struct
-import threading
+from ...hip.source_module import (STATIC, CHUNKS as _CHUNKS, chunk,
+                                   current_stream, suffix)
 
-_SOURCE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                       'posterior.hip')
-_FLAGS = ('-fno-fast-math',)
+_module = STATIC['posterior.hip']
+precompile = _module.precompile
 _BLOCK = 256
 _WAVES = 4          # rows of the inverse per workgroup of gp_rows (one per wave)
-_CHUNKS = (1, 2, 4, 8, 16)     # candidates per register chunk (template KC)
-_lock = threading.Lock()
-_kernels = None
 
 
 def source():
-    with open(_SOURCE) as f:
-        return f.read()
-
-
-def precompile():
-    """Compile into the JIT cache (hipcc, no device needed)."""
-    from ...hip import jit
-    return jit.compile_source(source(), _FLAGS)
-
-
-def _load():
-    global _kernels
-    with _lock:
-        if _kernels is None:
-            from ...hip import jit, runtime
-            mod = runtime.Module(jit.load_image(precompile()))
-            names = ['gp_finish']
-            names += [f'gp_rows_{t}_k{kc}' for t in ('f32', 'f64')
-                      for kc in _CHUNKS]
-            _kernels = {name: mod.function(name) for name in names}
-            _kernels['module'] = mod
-    return _kernels
+    return _module.source
 
 
 def grid(n, b):
     """(chunk size KC, row blocks, chunks): gp_rows runs row blocks x chunks
     workgroups.  A function of the shapes alone, so that the order of every
     sum is the same on every call."""
-    kc = next(k for k in _CHUNKS if k >= min(max(b, 1), _CHUNKS[-1]))
+    kc = chunk(b)
     return kc, -(-n // _WAVES), max(1, -(-b // kc))
 
 
@@ -90,7 +64,6 @@ def posterior(Kinv, Ks, Ky, kss, ymean=0.0, ystd=1.0, return_T=False):
     float32 or float64, column-major (`column_major`).  Ky: (n,), kss: (b,)
     float64, contiguous."""
     import torch
-    from ...hip import runtime
     if not Kinv.is_cuda:
         raise TypeError('posterior runs on CUDA tensors; see posterior_torch')
     n, b = _check(Kinv, Ks, Ky, kss)
@@ -111,25 +84,17 @@ def posterior(Kinv, Ks, Ky, kss, ymean=0.0, ystd=1.0, return_T=False):
             out[:b] = float(ymean)
             out[b:] = float(ystd) * torch.sqrt(torch.clamp(kss, min=0))
             return out, T
-        stream = torch.cuda.current_stream().cuda_stream or None
-        fn = _load()
+        stream = current_stream(dev)
         kc, nblk, gz = grid(n, b)
         partial = torch.empty(2 * b * nblk, dtype=torch.float64, device=dev)
-        sfx = 'f32' if Ks.dtype == torch.float32 else 'f64'
-        runtime.launch(
-            fn[f'gp_rows_{sfx}_k{kc}'], nblk * gz, _BLOCK,
-            struct.pack('@QQQqiqQQ', Kinv.data_ptr(), Ks.data_ptr(),
-                        Ky.data_ptr(), n, b, nblk, partial.data_ptr(),
-                        T.data_ptr() if return_T else 0),
+        _module.launch(
+            f'gp_rows_{suffix(Ks.dtype)}_k{kc}', nblk * gz, _BLOCK,
+            'QQQqiqQQ', Kinv.data_ptr(), Ks.data_ptr(), Ky.data_ptr(), n, b,
+            nblk, partial.data_ptr(), T.data_ptr() if return_T else 0,
             stream=stream)
-        runtime.launch(
-            fn['gp_finish'], b, _BLOCK,
-            struct.pack('@QqiQddQ', partial.data_ptr(), nblk, b,
-                        kss.data_ptr(), float(ymean), float(ystd),
-                        out.data_ptr()),
-            stream=stream)
-        # (the workspace is freed into torch's cache on this stream: the
-        # allocator hands it out again only behind these launches)
+        _module.launch('gp_finish', b, _BLOCK, 'QqiQddQ', partial.data_ptr(),
+                       nblk, b, kss.data_ptr(), float(ymean), float(ystd),
+                       out.data_ptr(), stream=stream)
     return out, T
 
 

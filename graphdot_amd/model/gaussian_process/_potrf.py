@@ -4,37 +4,10 @@ no fast-math) and runs it on float64 torch tensors.  The launch goes to
 torch's *current* stream of the tensor's device, so that it is ordered
 against the torch operations around it (the clone before, whatever reads the
 inverse after) whatever stream the caller works on."""
-import os
-import struct
-import threading
+from ...hip.source_module import STATIC, current_stream
 
-_SOURCE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                       'potrf.hip')
-_FLAGS = ('-fno-fast-math',)
+_module = STATIC['potrf.hip']
 _B = 64
-_lock = threading.Lock()
-_kernels = None
-
-
-def source():
-    with open(_SOURCE) as f:
-        return f.read()
-
-
-def precompile():
-    """Compile into the JIT cache (hipcc, no device needed)."""
-    from ...hip import jit
-    return jit.compile_source(source(), _FLAGS)
-
-
-def _load():
-    global _kernels
-    with _lock:
-        if _kernels is None:
-            from ...hip import jit, runtime
-            mod = runtime.Module(jit.load_image(precompile()))
-            _kernels = (mod, mod.function('spd_factor_invert_f64'))
-    return _kernels
 
 
 class FactorisationError(RuntimeError):
@@ -49,13 +22,10 @@ def _dataflow(A, invert, stamps=None):
     diagonal blocks] -- one small download tells the caller whether the
     launch completed and what log|L| is."""
     import torch
-    from ...hip import runtime
     n = A.shape[0]
     nb = -(-n // _B)
     ld = A.stride(0) if n > 1 else 1
-    fn = _load()[1]
     with torch.cuda.device(A.device):
-        stream = torch.cuda.current_stream().cuda_stream or None
         head = torch.zeros(16 + 2 * nb + 2 * nb * nb, dtype=torch.int32,
                            device=A.device)
         linv = torch.empty(nb * _B * _B, dtype=torch.float64, device=A.device)
@@ -66,17 +36,15 @@ def _dataflow(A, invert, stamps=None):
         else:
             Kinv = Z = None
     roles = nb * nb + (nb * (nb + 1) // 2 if invert else 0)
-    args = struct.pack('<QQQQQiiiiQ', A.data_ptr(),
-                       Kinv.data_ptr() if invert else 0,
-                       Z.data_ptr() if invert else 0, linv.data_ptr(),
-                       head.data_ptr(), ld, n, n, 1 if invert else 0,
-                       stamps.data_ptr() if stamps is not None else 0)
     # (roles are handed out by an atomic counter in dependency order: any
     # grid size is deadlock-free; 512 = two workgroups per compute unit)
-    runtime.launch(fn, min(roles, 512), 256, args, stream=stream)
-    # keep the workspaces alive until the stream has passed the launch: the
-    # caching allocator ties the blocks to the current stream, and every
-    # later use of them is ordered behind the launch there
+    _module.launch('spd_factor_invert_f64', min(roles, 512), 256,
+                   'QQQQQiiiiQ', A.data_ptr(),
+                   Kinv.data_ptr() if invert else 0,
+                   Z.data_ptr() if invert else 0, linv.data_ptr(),
+                   head.data_ptr(), ld, n, n, 1 if invert else 0,
+                   stamps.data_ptr() if stamps is not None else 0,
+                   stream=current_stream(A.device))
     return Kinv, head
 
 

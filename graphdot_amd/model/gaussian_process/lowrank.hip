@@ -21,17 +21,7 @@
 // lr_reduce (stage 2): one workgroup per plane sums its nblk partials in a
 // fixed order.  The grid is a function of the shapes alone and there are no
 // atomics, so the result is the same bits on every call.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#define BLOCK 256
-#define WAVE 64
-#define NWAVE (BLOCK / WAVE)
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
+#include "dense_reduce.h"
 
 template <typename T, int KC>
 __device__ __forceinline__ void contract_stage1(
@@ -106,17 +96,5 @@ extern "C" __global__ __launch_bounds__(BLOCK) void
 lr_reduce(const double *__restrict__ partial, int64_t nblk,
           double *__restrict__ out)
 {
-    __shared__ double red[NWAVE];
-    const double *p = partial + (int64_t)blockIdx.x * nblk;
-    double s = 0.0;
-    for (int64_t b = threadIdx.x; b < nblk; b += BLOCK) s += p[b];
-    s = wave_sum(s);
-    const int lane = threadIdx.x % WAVE, wid = threadIdx.x / WAVE;
-    if (lane == 0) red[wid] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < NWAVE; ++w) t += red[w];
-        out[blockIdx.x] = t;
-    }
+    reduce_partials(partial, nblk, out);
 }

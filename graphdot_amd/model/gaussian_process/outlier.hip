@@ -24,30 +24,10 @@
 // od_reduce (stage C): one workgroup per scalar sums its inputs in a fixed
 // order; the others copy d_alpha into place.  The grids are functions of the
 // shapes alone and there are no atomics: the same bits on every call.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "dense_reduce.h"
 
-#define BLOCK 256
-#define WAVE 64
-#define NWAVE (BLOCK / WAVE)
 #define TILE 64
 #define SUB 4                    // column blocks per tile (TILE / SUB columns)
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
-
-// NaN-propagating maximum (a NaN row sum must fail the certificate)
-__device__ __forceinline__ double nanmax(double a, double b) {
-    return (a != a || a > b) ? a : b;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-        v = nanmax(v, __shfl_xor(v, off, WAVE));
-    return v;
-}
 
 // rows: [a (n), a * y (n), d_alpha (n), |K_sigma| row sums (n), |Kinv| row
 // sums (n)]; gridDim.x = ceil(n / NWAVE)

@@ -26,13 +26,8 @@
 // order and applies the epilogue.  The grids and the order of every sum are
 // functions of (n, b) alone and there are no atomics: the same bits on every
 // call.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "dense_reduce.h"
 #include "wave.h"
-
-#define BLOCK 256
-#define WAVE 64
-#define NWAVE (BLOCK / WAVE)
 
 template <typename T, int KC>
 __device__ __forceinline__ void rows_stage(
