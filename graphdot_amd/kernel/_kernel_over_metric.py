@@ -21,6 +21,7 @@ import functools
 import numpy as np
 import sympy
 from ..util.pretty_tuple import pretty_tuple
+from ._device_path import NoDevicePath, active_planes
 
 #: what the host evaluation of a formula may call (scipy: special functions
 #: such as besselk, which have no device spelling)
@@ -163,7 +164,7 @@ class KernelOverMetric:
 
     # -- device path ---------------------------------------------------------------
     def _map(self):
-        """The compiled element-wise map; TypeError if the formula or one of
+        """The compiled element-wise map; NoDevicePath if the formula or one of
         its derivatives has no device spelling."""
         if self._device_map is None:
             from ._kom_map import device_map
@@ -173,10 +174,10 @@ class KernelOverMetric:
 
     def _device_inputs(self, X, Y, eval_gradient):
         """(map, D, dD planes, active plane indices) on the GPU from the
-        distance's ``device_distance``; TypeError where there is none."""
+        distance's ``device_distance``; NoDevicePath where there is none."""
         fn = getattr(self.distance, 'device_distance', None)
         if fn is None:
-            raise TypeError('the distance has no device_distance')
+            raise NoDevicePath('the distance has no device_distance')
         dmap = self._map()
         import torch
         torch.cuda.is_available()    # (torch's HIP runtime before libgdhip's)
@@ -186,14 +187,11 @@ class KernelOverMetric:
         planes = np.zeros(0, dtype=np.int64)
         if dD is not None:
             dD = torch.as_tensor(dD, device='cuda')
-            mask = np.asarray(getattr(self.distance, 'active_theta_mask',
-                                      np.ones(dD.shape[2], dtype=bool)))
-            planes = np.flatnonzero(mask) if len(mask) == dD.shape[2] \
-                else np.arange(dD.shape[2])
+            planes = active_planes(self.distance, dD.shape[2])
             if len(planes) != len(self.distance.theta):
-                raise TypeError('the distance gradient has '
-                                f'{len(planes)} active columns, its theta '
-                                f'{len(self.distance.theta)}')
+                raise NoDevicePath('the distance gradient has '
+                                   f'{len(planes)} active columns, its theta '
+                                   f'{len(self.distance.theta)}')
         return dmap, D, dD, planes
 
     def _h(self):
@@ -203,7 +201,7 @@ class KernelOverMetric:
         """`__call__(X)` on the GPU: K as a float64 torch tensor and, with
         `eval_gradient`, the dense float64 (n, n, len(theta)) gradient,
         column-major.  (`local_gradient` is accepted for the regressor's call
-        and not forwarded, as in kernel/fix.py.)  TypeError if the distance
+        and not forwarded, as in kernel/fix.py.)  NoDevicePath if the distance
         or the formula has no device path."""
         dmap, D, dD, planes = self._device_inputs(X, None, eval_gradient)
         if not eval_gradient:
@@ -233,7 +231,7 @@ class KernelOverMetric:
         `eval_gradient`, df/dh at 0 followed by zeros for the distance's
         columns (a distance vanishes on the diagonal)."""
         if getattr(self.distance, 'device_distance', None) is None:
-            raise TypeError('the distance has no device_distance')
+            raise NoDevicePath('the distance has no device_distance')
         import torch
         n = len(X)
         z = np.zeros(1)

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import sympy
 from ..hip.source_module import SourceModule, current_stream, suffix
+from ._device_path import NoDevicePath
 
 _TEMPLATE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                          'kernel_over_metric.hip')
@@ -21,21 +22,21 @@ _BLOCK = 256
 
 
 def _print(expr, symbols):
-    """Device C++ (float64) for `expr`; TypeError if the printer cannot
+    """Device C++ (float64) for `expr`; NoDevicePath if the printer cannot
     express it."""
     from ..codegen.sympy_printer import hipcxxcode, to_real_expr
     try:
         text = hipcxxcode(expr, symbols)
     except Exception as e:   # (PrintMethodNotImplementedError and kin)
-        raise TypeError(f'no device spelling for {expr}: {e}') from None
+        raise NoDevicePath(f'no device spelling for {expr}: {e}') from None
     if 'Not supported' in text or 'not supported' in text:
-        raise TypeError(f'no device spelling for {expr}')
+        raise NoDevicePath(f'no device spelling for {expr}')
     return to_real_expr(text, 'float64')
 
 
 def generate(expr, x, names):
     """The HIP source of the map for ``f = expr(x; names)``: f, df/dx and
-    df/dh for every name in order.  TypeError where the printer cannot
+    df/dh for every name in order.  NoDevicePath where the printer cannot
     express one of them."""
     from ..codegen import Template
     expr = sympy.sympify(expr)
@@ -45,8 +46,8 @@ def generate(expr, x, names):
     symbols.update({h: f'H.h[{k}]' for k, h in enumerate(names)})
     for s in expr.free_symbols:
         if str(s) not in symbols:
-            raise TypeError(f'free symbol {s} is neither the distance '
-                            f'{x!r} nor a hyperparameter')
+            raise NoDevicePath(f'free symbol {s} is neither the distance '
+                               f'{x!r} nor a hyperparameter')
     fun = _print(expr, symbols)
     dfdx = _print(sympy.diff(expr, xs), symbols)
     own = [f'    G[e + N * {k}] = {_print(sympy.diff(expr, h), symbols)};'

@@ -11,6 +11,7 @@ the two diagonals.
 import copy
 import numpy as np
 from ..util.pretty_tuple import pretty_tuple
+from ._device_path import NoDevicePath
 
 
 class _Transformed:
@@ -52,10 +53,10 @@ class _Transformed:
 
     def _inner_device_gram(self, X, eval_gradient):
         """float64 torch tensors (K, dK over all hyperparameter columns) of
-        the wrapped kernel on the GPU; TypeError if it has no device path."""
+        the wrapped kernel on the GPU; NoDevicePath if it has none."""
         inner = getattr(self.kernel, 'device_gram', None)
         if inner is None:
-            raise TypeError('the wrapped kernel has no device_gram')
+            raise NoDevicePath('the wrapped kernel has no device_gram')
         import torch
         out = inner(X, eval_gradient=eval_gradient)
         R, dR = out if eval_gradient else (out, None)
@@ -67,10 +68,10 @@ class _Transformed:
     def _inner_cross(self, X, Y, eval_gradient):
         """float64 torch tensor of the wrapped kernel's ``(X, Y)`` matrix
         and its gradient as a `LazyGradient`, from the kernel's device
-        methods; TypeError if it has none."""
+        methods; NoDevicePath if it has none."""
         inner = getattr(self.kernel, 'device_cross_gram', None)
         if inner is None:
-            raise TypeError('the wrapped kernel has no device_cross_gram')
+            raise NoDevicePath('the wrapped kernel has no device_cross_gram')
         import torch
         out = inner(X, Y, eval_gradient=eval_gradient)
         R, dR = out if eval_gradient else (out, None)
@@ -83,7 +84,7 @@ class _Transformed:
         """float64 torch tensors of the wrapped kernel's `device_diag`."""
         inner = getattr(self.kernel, 'device_diag', None)
         if inner is None:
-            raise TypeError('the wrapped kernel has no device_diag')
+            raise NoDevicePath('the wrapped kernel has no device_diag')
         import torch
         out = inner(X, eval_gradient=eval_gradient)
         d, dd = out if eval_gradient else (out, None)

@@ -20,6 +20,7 @@ from ...hip import hostlib
 from ...util import Timer
 from ...util.iterable import fold_like, flatten, replace
 from ...util.pretty_tuple import pretty_tuple
+from .._device_path import NoDevicePath
 from ._backend_factory import backend_factory
 from .starting_probability import StartingProbability, Uniform, Adhoc
 
@@ -306,7 +307,7 @@ class MarginalizedGraphKernel:
         from ...hip.runtime import DeviceArray
         backend = self.backend
         if not hasattr(backend, 'prepare'):
-            raise TypeError('device_gram needs the HIP backend')
+            raise NoDevicePath('device_gram needs the HIP backend')
         pred = Graph.has_unified_types(X)
         if pred is not True:
             raise _type_error(
@@ -365,9 +366,9 @@ class MarginalizedGraphKernel:
     def _device_backend(self, what):
         backend = self.backend
         if not hasattr(backend, 'prepare'):
-            raise TypeError(f'{what} needs the HIP backend')
+            raise NoDevicePath(f'{what} needs the HIP backend')
         if getattr(backend, 'shards_over_ranks', lambda: False)():
-            raise TypeError(f'{what}: no pair-sharded evaluation')
+            raise NoDevicePath(f'{what}: no pair-sharded evaluation')
         return backend
 
     def _device_result(self, backend, graphs, jobs, starts, nX, nY, shape,
@@ -410,7 +411,7 @@ class MarginalizedGraphKernel:
         Unlike `device_gram`'s, these views own their buffers: a later
         evaluation on the same backend does not overwrite them, and the
         memory is released when the last view (or a torch tensor that adopted
-        it) is gone.  TypeError if the backend is not HIP, or shards pairs
+        it) is gone.  NoDevicePath if the backend is not HIP, or shards pairs
         over ranks."""
         backend = self._device_backend('device_cross_gram')
         all_graphs = list(it.chain(X, Y))

@@ -191,27 +191,28 @@ class MaxiMin(MarginalizedGraphKernel):
         left in device memory: views (`graphdot_amd.hip.runtime.DeviceArray`)
         in the backend's arithmetic, column-major, that own their buffers
         like `device_cross_gram`'s.  The same launches as `__call__`, so the
-        same values.  TypeError where the fused evaluation does not apply: a
+        same values.  NoDevicePath where the fused evaluation does not apply: a
         backend that is not HIP, pairs sharded over ranks, graphs the
         owner-computes solvers do not cover, attribute types not unified."""
         from ...hip.runtime import DeviceArray
+        from ...kernel._device_path import NoDevicePath
         from ...kernel.marginalized._backend_hip import NotOwnerComputes
         backend = self._fused_backend()
         if backend is None or not hasattr(backend, 'maximin_distance_device'):
-            raise TypeError('device_distance needs the HIP backend, '
-                            'unsharded')
+            raise NoDevicePath('device_distance needs the HIP backend, '
+                               'unsharded')
         args = self._maximin_args(X, Y, eval_gradient, lmin)
         if args is None:
-            raise TypeError('device_distance: graph attribute types differ')
+            raise NoDevicePath('device_distance: graph attribute types differ')
         nx, ny = args[9], args[10]
         if nx == 0 or ny == 0:
-            raise TypeError('device_distance: no pairs')
+            raise NoDevicePath('device_distance: no pairs')
         try:
             plan = backend.maximin_distance_device(
                 *args, reference_compat=self.reference_compat)
         except NotOwnerComputes:
-            raise TypeError('device_distance: graphs beyond the '
-                            'owner-computes solvers') from None
+            raise NoDevicePath('device_distance: graphs beyond the '
+                               'owner-computes solvers') from None
         real = np.dtype(backend.real)
         D = DeviceArray.fortran(plan.buffers['gramian'].ptr, (nx, ny), real,
                                 owner=plan)

@@ -44,21 +44,6 @@ def resolve_device(device):
     return device
 
 
-def _device_path(kernel):
-    """Does `kernel` compute its Gram matrix in device memory?  The
-    marginalized graph kernel on the HIP backend does (`device_gram`), and so
-    do the wrappers of kernel/fix.py around one that does."""
-    k = kernel
-    while k is not None:
-        if not callable(getattr(k, 'device_gram', None)):
-            return False
-        backend = getattr(k, 'backend', None)
-        if backend is not None:
-            return hasattr(backend, 'prepare')     # the HIP backend
-        k = getattr(k, 'kernel', None)
-    return False
-
-
 def gram(selector, X, device):
     """The square kernel matrix of `X` for `selector` (its `kernel` and
     `kernel_options`): a numpy array on the host for device 'cpu', a CUDA
@@ -74,13 +59,16 @@ def gram(selector, X, device):
             X.shape[0] == X.shape[1]
         ), 'A precomputed kernel matrix must be square.'
         K = X
-    elif device == 'cuda' and not selector.kernel_options \
-            and _device_path(selector.kernel):
-        K = selector.kernel.device_gram(X)
-        if not isinstance(K, torch.Tensor):
-            K = torch.as_tensor(K, device='cuda')
     else:
-        K = selector.kernel(X, **selector.kernel_options)
+        from .._device_kernel import device_call
+        K = None
+        if device == 'cuda' and not selector.kernel_options:
+            # (None: the kernel has no device path)
+            K = device_call(selector.kernel, 'device_gram', X)
+        if K is None:
+            K = selector.kernel(X, **selector.kernel_options)
+        elif not isinstance(K, torch.Tensor):
+            K = torch.as_tensor(K, device='cuda')
     if device == 'cpu':
         if torch is not None and isinstance(K, torch.Tensor):
             K = K.detach().cpu().numpy()

@@ -8,8 +8,9 @@ stored.
 """
 import warnings
 import numpy as np
-from scipy.optimize import minimize
 import scipy.linalg
+from .._device_kernel import device_call, as_float64, active_planes
+from .._fit import multistart
 
 _NOT_PD = ('The Graph Laplacian is not positive definite. Some'
            'weights on edges may be invalid.')
@@ -40,11 +41,12 @@ def _fused_reason(weight):
     if not isinstance(inner, MarginalizedGraphKernel):
         return ('the kernel is neither a MarginalizedGraphKernel nor '
                 'Normalization of one')
-    backend = inner.backend
-    if not hasattr(backend, 'prepare'):
+    # (the kernel's own answer, without a launch: what its device methods
+    # ask before they evaluate anything)
+    if device_call(inner, '_device_backend', 'the fused path') is None:
+        if getattr(inner.backend, 'shards_over_ranks', lambda: False)():
+            return 'the graph kernel shards its pairs over ranks'
         return 'the graph kernel is not on the HIP backend'
-    if getattr(backend, 'shards_over_ranks', lambda: False)():
-        return 'the graph kernel shards its pairs over ranks'
     return None
 
 
@@ -144,11 +146,10 @@ class GaussianFieldRegressor:
                 yield x0
                 yield from x0 + theta_jitter * np.random.randn(n - 1, len(x0))
 
-            opt = self._hyper_opt(
-                method=self.optimizer,
-                fun=lambda theta, objective=objective: objective(
-                    X, y, theta=theta, eval_gradient=True, verbose=verbose),
-                xgen=xgen(repeat), tol=tol, verbose=verbose)
+            opt = multistart(
+                lambda theta: objective(X, y, theta=theta, eval_gradient=True,
+                                        verbose=verbose),
+                xgen(repeat), self.optimizer, self.weight.bounds, tol)
             if verbose:
                 print(f'Optimization result:\n{opt}')
 
@@ -181,15 +182,6 @@ class GaussianFieldRegressor:
         self.fit(X, y, loss=loss, tol=tol, repeat=repeat,
                  theta_jitter=theta_jitter, verbose=verbose)
         return self.predict(X, y, return_influence=return_influence)
-
-    def _hyper_opt(self, method, fun, xgen, tol, verbose):
-        opt = None
-        for x in xgen:
-            opt_local = minimize(fun=fun, method=method, x0=x,
-                                 bounds=self.weight.bounds, jac=True, tol=tol)
-            if not opt or (opt_local.success and opt_local.fun < opt.fun):
-                opt = opt_local
-        return opt
 
     def average_label_entropy(self, X, y, theta=None, eval_gradient=False,
                               verbose=False):
@@ -326,11 +318,6 @@ class GaussianFieldRegressor:
         return f_u, solve, ((dW_uu, f_u), (dW_ul, f_l))
 
     # -- the fused device path ---------------------------------------------------------
-    @staticmethod
-    def _planes(kernel):
-        """Planes of the active hyperparameters."""
-        return np.flatnonzero(np.asarray(kernel.active_theta_mask))
-
     def _self_block(self, kernel, X, jac):
         """X against itself by ``device_gram``; self-similarities from its
         diagonal, as in ``KernelInducedDistance(X)``."""
@@ -341,8 +328,8 @@ class GaussianFieldRegressor:
         kd = K.diagonal().to(torch.float64)
         b = dict(K=K, kr=kd, kc=kd, self_block=True)
         if jac:
-            planes = self._planes(kernel)
             P = torch.as_tensor(dK, device='cuda')
+            planes = active_planes(kernel, P.shape[2])
             idx = torch.as_tensor(planes, device='cuda')
             dkd = P.diagonal(dim1=0, dim2=1).T.index_select(1, idx).to(
                 torch.float64)
@@ -361,29 +348,28 @@ class GaussianFieldRegressor:
         (kx, dkx), (ky, dky) = (dx, dy) if jac else ((dx, None), (dy, None))
         K = torch.as_tensor(K, device='cuda')
         b = dict(K=K, self_block=False,
-                 kr=torch.as_tensor(kx, device='cuda').to(torch.float64),
-                 kc=torch.as_tensor(ky, device='cuda').to(torch.float64))
+                 kr=as_float64(kx, 'cuda'), kc=as_float64(ky, 'cuda'))
         if not jac:
             return b
-        planes = self._planes(kernel)
+        lazy = isinstance(dK, LazyGradient)
+        P = dK.planes if lazy else torch.as_tensor(dK, device='cuda')
+        planes = active_planes(kernel, P.shape[2])
         idx = torch.as_tensor(planes, device='cuda')
 
         def cols(a):
             return torch.as_tensor(a, device='cuda').index_select(
                 1, idx).to(torch.float64)
-        b.update(planes=planes, dkr=cols(dkx), dkc=cols(dky))
-        if isinstance(dK, LazyGradient):
+        b.update(P=P, planes=planes, dkr=cols(dkx), dkc=cols(dky))
+        if lazy:
             # Normalization: s_i t_c P + K (u_i + v_c)
             if dK.lead is not None or dK.scale is not None \
                     or len(dK.terms) > 1 or any(
                         L.data_ptr() != K.data_ptr() for L, _, _ in dK.terms):
                 raise TypeError('a gradient form the field kernels do not '
                                 'take')
-            b.update(P=dK.planes, row=dK.row, col=dK.col)
+            b.update(row=dK.row, col=dK.col)
             for _, u, v in dK.terms:
                 b.update(u=cols(u), v=cols(v))
-        else:
-            b['P'] = torch.as_tensor(dK, device='cuda')
         return b
 
     def _rowsums(self, b, y=None, write=False):

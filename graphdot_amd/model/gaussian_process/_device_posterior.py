@@ -7,6 +7,7 @@ the fused kernels of posterior.hip, which stream the inverse once for all
 candidates; one download of ``2 b`` numbers per call."""
 import numpy as np
 
+from .._device_kernel import device_call, on_device
 from .gpr import GaussianProcessRegressor, _torch
 from . import _posterior
 
@@ -17,10 +18,10 @@ class DevicePosterior:
 
     `available` says whether the device path applies: the regressor's dense
     algebra is on a CUDA device, it has no `kernel_options`, and its kernel
-    offers `device_cross_gram` and `device_diag` that do not raise TypeError
-    (the HIP backend, not sharded over ranks).  Otherwise `predict` is
-    `gpr.predict`.  After a refit of `gpr` the device copies are rebuilt on
-    the next call."""
+    offers `device_cross_gram` and a `device_diag` that does not raise
+    `NoDevicePath` (the HIP backend, not sharded over ranks).  Otherwise
+    `predict` is `gpr.predict`.  After a refit of `gpr` the device copies are
+    rebuilt on the next call."""
 
     def __init__(self, gpr):
         if not isinstance(gpr, GaussianProcessRegressor):
@@ -42,16 +43,11 @@ class DevicePosterior:
 
     def _probe(self, la):
         kernel = self.gpr.kernel
-        if la.device.type != 'cuda' or self.gpr.kernel_options:
+        if not on_device(la, self.gpr.kernel_options) \
+                or not hasattr(kernel, 'device_cross_gram'):
             return False
-        if not (hasattr(kernel, 'device_cross_gram')
-                and hasattr(kernel, 'device_diag')):
-            return False
-        try:
-            kernel.device_diag(self.X[:1])
-        except TypeError:           # not the HIP backend, or pair-sharded
-            return False
-        return True
+        # (one graph's self-similarity: a launch, the answer of the backend)
+        return device_call(kernel, 'device_diag', self.X[:1]) is not None
 
     def _current(self):
         if self.gpr.Kinv is not self._fitted:

@@ -65,6 +65,24 @@ def read_head(head, nb):
     return parse_head(head[:16 + 2 * nb].cpu().numpy(), nb)
 
 
+def packed_head(head, nb):
+    """The head of `factor_inverse` as a float64 tensor, for the caller to
+    concatenate with its own float64 results into ONE download."""
+    import torch
+    return head[:16 + 2 * nb].view(torch.float64)
+
+
+def logdet(packed, nb):
+    """(``log|K|``, the caller's own numbers) from a download that starts
+    with `packed_head`.  NaN when `K` is not positive definite;
+    `FactorisationError` when the launch did not complete."""
+    completed, logdet_l = parse_head(packed[:8 + nb], nb)
+    if not completed:
+        raise FactorisationError(
+            'spd_factor_invert_f64 gave up waiting for a tile')
+    return 2.0 * logdet_l, packed[8 + nb:]
+
+
 def factor_inverse(K):
     """``K^-1`` and ``log|K|`` of the symmetric positive definite float64
     CUDA tensor `K` in ONE launch (potrf.hip, `spd_factor_invert_f64`):

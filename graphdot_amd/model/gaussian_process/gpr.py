@@ -23,11 +23,12 @@ from, so that one likelihood step of configuration 5 is kernel + a few ms;
 without a GPU the same code runs on torch's CPU backend (tests).
 """
 import os
-import pickle
 import time
 import warnings
 import numpy as np
-from scipy.optimize import minimize
+from .._device_kernel import (device_call, on_device, as_float64,
+                              active_planes)
+from ._base import GaussianProcessRegressorBase
 
 
 def _torch():
@@ -147,13 +148,10 @@ class _Dense:
             # and the log-determinant shares of the diagonal blocks -- the
             # only host synchronisation of the factorisation (a pivot that
             # is not positive makes the sum of logarithms NaN)
-            from ._potrf import factor_inverse, read_head, FactorisationError
-            Kinv, head, nb = factor_inverse(K)
-            completed, logdet = read_head(head, nb)
-            if not completed:
-                raise FactorisationError(
-                    'spd_factor_invert_f64 gave up waiting for a tile')
-            logdet *= 2.0
+            from . import _potrf
+            Kinv, head, nb = _potrf.factor_inverse(K)
+            logdet, _ = _potrf.logdet(
+                _potrf.packed_head(head, nb).cpu().numpy(), nb)
             if np.isfinite(logdet):
                 return Kinv, logdet
         else:
@@ -174,7 +172,7 @@ class _Dense:
         return Kinv, float(torch.log(w).sum())
 
 
-class GaussianProcessRegressor:
+class GaussianProcessRegressor(GaussianProcessRegressorBase):
     """Gaussian process regression.
 
     Parameters
@@ -201,90 +199,9 @@ class GaussianProcessRegressor:
     def __init__(self, kernel, alpha=1e-8, beta=1e-8, optimizer=None,
                  normalize_y=False, regularization='+', kernel_options={},
                  device='auto'):
-        self.kernel = kernel
+        super().__init__(kernel, beta, optimizer, normalize_y, regularization,
+                         kernel_options, device)
         self.alpha = alpha
-        self.beta = beta
-        self.optimizer = 'L-BFGS-B' if optimizer is True else optimizer
-        self.normalize_y = normalize_y
-        self.regularization = regularization
-        self.kernel_options = dict(kernel_options)
-        self.device = device
-
-    # -- data ---------------------------------------------------------------
-    @property
-    def X(self):
-        try:
-            return self._X
-        except AttributeError:
-            raise AttributeError(
-                'Training data does not exist. Please provide using fit().')
-
-    @X.setter
-    def X(self, X):
-        self._X = np.asarray(X)
-
-    @property
-    def y(self):
-        try:
-            return self._y * self._ystd + self._ymean
-        except AttributeError:
-            raise AttributeError(
-                'Training data does not exist. Please provide using fit().')
-
-    @staticmethod
-    def mask(iterable):
-        """(mask of usable targets, the usable targets as float64)."""
-        values = list(iterable)
-        mask = np.array([v is not None and bool(np.isfinite(v))
-                         for v in values], dtype=bool)
-        masked = np.array([float(v) for v, m in zip(values, mask) if m],
-                          dtype=np.float64)
-        return mask, masked
-
-    @y.setter
-    def y(self, y):
-        self._y_mask, y_masked = self.mask(y)
-        if self.normalize_y is True:
-            self._ymean, self._ystd = y_masked.mean(), y_masked.std()
-            self._y = (y_masked - self._ymean) / self._ystd
-        else:
-            self._ymean, self._ystd = 0, 1
-            self._y = y_masked
-
-    # -- kernel matrices --------------------------------------------------------
-    def _regularize(self, K, alpha):
-        if self.regularization in ('+', 'additive'):
-            return K + alpha
-        if self.regularization in ('*', 'multiplicative'):
-            return K * (1 + alpha)
-        raise RuntimeError(
-            f'Unknown regularization method {self.regularization}.')
-
-    def _gramian(self, alpha, X, Y=None, kernel=None, jac=False, diag=False):
-        kernel = kernel or self.kernel
-        opts = self.kernel_options
-        if Y is not None:
-            if diag is True:
-                raise ValueError(
-                    'Diagonal Gramian does not exist between two sets.')
-            return kernel(X, Y, eval_gradient=True, **opts) if jac \
-                else kernel(X, Y, **opts)
-        if diag is True:
-            return self._regularize(kernel.diag(X, **opts), alpha)
-        if jac is True:
-            K, J = kernel(X, eval_gradient=True, **opts)
-        else:
-            K, J = kernel(X, **opts), None
-        K = np.array(K, dtype=np.float64)
-        step = len(K) + 1
-        K.flat[::step] = self._regularize(K.flat[::step], alpha)
-        return (K, J) if jac is True else K
-
-    def _dense(self):
-        if not isinstance(getattr(self, '_la', None), _Dense) \
-                or self._la_device != self.device:
-            self._la, self._la_device = _Dense(self.device), self.device
-        return self._la
 
     # -- fitting -----------------------------------------------------------------
     def fit(self, X, y, loss='likelihood', tol=1e-5, repeat=1,
@@ -300,28 +217,7 @@ class GaussianProcessRegressor:
                 objective = self.squared_loocv_error
             else:
                 raise RuntimeError(f'Unknown loss function: {loss}.')
-            x0 = np.array(self.kernel.theta, dtype=float)
-            starts = [x0] + [x0 + theta_jitter * np.random.randn(len(x0))
-                             for _ in range(repeat - 1)]
-            best = None
-            for x in starts:
-                res = minimize(
-                    fun=lambda t: objective(t, eval_gradient=True,
-                                            clone_kernel=False,
-                                            verbose=verbose),
-                    method=self.optimizer, x0=x, bounds=self.kernel.bounds,
-                    jac=True, tol=tol)
-                if best is None or (res.success and res.fun < best.fun):
-                    best = res
-            if verbose:
-                print(f'Optimization result:\n{best}')
-            if not best.success:
-                raise RuntimeError(
-                    f'Training using the {loss} loss did not converge, got:\n'
-                    f'{best}')
-            self.kernel.theta = best.x
-            #: the optimiser's report (scipy OptimizeResult: nit, nfev, fun)
-            self.optimization_result = best
+            self._optimize(objective, loss, tol, repeat, theta_jitter, verbose)
         la = self._dense()
         K = self._gramian(self.alpha, self._X)
         self.K = K = K[self._y_mask, :][:, self._y_mask]
@@ -370,18 +266,8 @@ class GaussianProcessRegressor:
     # -- objectives ----------------------------------------------------------------
     def _objective_inputs(self, theta, X, y, eval_gradient, clone_kernel,
                           local_gradient=False):
-        theta = np.array(theta if theta is not None else self.kernel.theta,
-                         dtype=float)
-        X = X if X is not None else self._X
-        if y is not None:
-            y_mask, y = self.mask(y)
-        else:
-            y, y_mask = self._y, self._y_mask
-        if clone_kernel is True:
-            kernel = self.kernel.clone_with_theta(theta)
-        else:
-            kernel = self.kernel
-            kernel.theta = theta
+        theta, X, y, y_mask, kernel = self._prologue(theta, X, y,
+                                                     clone_kernel)
         t = time.perf_counter()
         la = self._dense()
         on_device = self._device_gramian(la, kernel, X, eval_gradient,
@@ -413,18 +299,16 @@ class GaussianProcessRegressor:
         kernel options are in the way; None otherwise.  `local_gradient`:
         accept this rank's share of a pair-sharded gradient
         (`LocalGradient`) in place of the planes."""
-        if la.device.type != 'cuda' or self.kernel_options \
-                or not hasattr(kernel, 'device_gram'):
+        if not on_device(la, self.kernel_options):
             return None
         torch = _torch()
-        try:
-            out = kernel.device_gram(X, eval_gradient=jac,
-                                     **({'local_gradient': 'overlapped'}
-                                        if jac and local_gradient else {}))
-        except TypeError:            # not the HIP backend
+        out = device_call(kernel, 'device_gram', X, eval_gradient=jac,
+                          **({'local_gradient': 'overlapped'}
+                             if jac and local_gradient else {}))
+        if out is None:
             return None
         Kd, dKd = out if jac else (out, None)
-        K = torch.as_tensor(Kd, device=la.device).to(torch.float64)
+        K = as_float64(Kd, la.device)
         diag = torch.diagonal(K)
         diag.copy_(self._regularize(diag, self.alpha))
         dK = None
@@ -440,10 +324,10 @@ class GaussianProcessRegressor:
             dK = torch.as_tensor(dKd, device=la.device)
             # a graph kernel hands over all its columns; transformers
             # (kernel/fix.py) already work on what the kernel protocol returns
-            mask = np.asarray(kernel.active_theta_mask)
-            if dK.shape[2] == len(mask) and not mask.all():
-                dK = dK.index_select(2, torch.as_tensor(
-                    np.flatnonzero(mask), device=la.device))
+            planes = active_planes(kernel, dK.shape[2])
+            if len(planes) != dK.shape[2]:
+                dK = dK.index_select(2, torch.as_tensor(planes,
+                                                        device=la.device))
             dK = dK.to(torch.float64)
         return K, dK
 
@@ -463,26 +347,20 @@ class GaussianProcessRegressor:
             # potrf.hip, then ONE download: the launch's status word and
             # log-determinant shares, y^T K^-1 y and the gradient's
             # contractions (round 5: three host synchronisations)
-            from ._potrf import factor_inverse, parse_head, FactorisationError
-            Kinv, head, nb = factor_inverse(K)
+            from . import _potrf
+            Kinv, head, nb = _potrf.factor_inverse(K)
             Ky = Kinv @ y
-            parts = [head[:16 + 2 * nb].view(torch.float64),
-                     (y @ Ky).reshape(1)]
+            parts = [_potrf.packed_head(head, nb), (y @ Ky).reshape(1)]
             if eval_gradient is True:
                 W = Kinv - torch.outer(Ky, Ky)
                 parts.append(_contract_local(W, dK, self._keep)
                              if hasattr(dK, 'columns')
                              else _contract_planes(W, dK))
-            packed = torch.cat(parts).cpu().numpy()
-            completed, logdet = parse_head(packed[:8 + nb], nb)
-            if not completed:
-                raise FactorisationError(
-                    'spd_factor_invert_f64 gave up waiting for a tile')
-            logdet *= 2.0
+            logdet, packed = _potrf.logdet(torch.cat(parts).cpu().numpy(), nb)
             if np.isfinite(logdet):       # (else: not positive definite)
-                yKy = float(packed[8 + nb])
+                yKy = float(packed[0])
                 if eval_gradient is True:
-                    grad = packed[9 + nb:] * np.exp(theta)
+                    grad = packed[1:] * np.exp(theta)
                 done = True
         if not done:
             Kinv, logdet = la.factor(K, self.beta, try_native=False)
@@ -537,25 +415,3 @@ class GaussianProcessRegressor:
                   f't_kernel {t_kernel:8.2g} s  t_linalg {t_linalg:8.2g} s')
         self.last_timing = {'kernel': t_kernel, 'linalg': t_linalg}
         return (value, grad) if eval_gradient is True else value
-
-    # -- persistence ---------------------------------------------------------------
-    def save(self, path, filename='model.pkl', overwrite=False):
-        """Pickle the trained state (without the kernel object; its
-        hyperparameters are stored as `theta`)."""
-        f_model = os.path.join(path, filename)
-        if os.path.isfile(f_model) and not overwrite:
-            raise RuntimeError(
-                f'Path {f_model} already exists. To overwrite, set '
-                '`overwrite=True`.')
-        store = {k: v for k, v in self.__dict__.items()
-                 if k not in ('kernel', '_la')}
-        store['theta'] = np.array(self.kernel.theta)
-        with open(f_model, 'wb') as f:
-            pickle.dump(store, f, protocol=4)
-
-    def load(self, path, filename='model.pkl'):
-        with open(os.path.join(path, filename), 'rb') as f:
-            store = pickle.load(f)
-        theta = store.pop('theta')
-        self.__dict__.update(**store)
-        self.kernel.theta = theta

@@ -25,8 +25,10 @@ the reference:
 import time
 import warnings
 import numpy as np
-from scipy.optimize import minimize
-from .gpr import GaussianProcessRegressor, _Dense, _torch
+from .._device_kernel import (device_call, on_device, as_float64,
+                              active_planes)
+from ._base import GaussianProcessRegressorBase
+from .gpr import _torch
 
 
 def _column_major(t):
@@ -67,7 +69,7 @@ class _LowRank:
         return ((self.U / self.S)**2).sum(1)
 
 
-class LowRankApproximateGPR:
+class LowRankApproximateGPR(GaussianProcessRegressorBase):
     """Gaussian process regression in the Nystrom low-rank approximation.
 
     Parameters
@@ -96,20 +98,9 @@ class LowRankApproximateGPR:
     def __init__(self, kernel, alpha=1e-7, beta=1e-7, optimizer=None,
                  normalize_y=False, regularization='+', kernel_options={},
                  device='auto'):
-        self.kernel = kernel
+        super().__init__(kernel, beta, optimizer, normalize_y, regularization,
+                         kernel_options, device)
         self.alpha = alpha
-        self.beta = beta
-        self.optimizer = 'L-BFGS-B' if optimizer is True else optimizer
-        self.normalize_y = normalize_y
-        self.regularization = regularization
-        self.kernel_options = dict(kernel_options)
-        self.device = device
-
-    # -- data: as in GaussianProcessRegressor ----------------------------------
-    X = GaussianProcessRegressor.X
-    y = GaussianProcessRegressor.y
-    mask = staticmethod(GaussianProcessRegressor.mask)
-    _regularize = GaussianProcessRegressor._regularize
 
     @property
     def C(self):
@@ -124,36 +115,29 @@ class LowRankApproximateGPR:
     def C(self, C):
         self._C = C
 
-    def _dense(self):
-        if not isinstance(getattr(self, '_la', None), _Dense) \
-                or self._la_device != self.device:
-            self._la, self._la_device = _Dense(self.device), self.device
-        return self._la
-
     # -- kernel evaluations: float64 tensors on the algebra's device ------------
-    def _on_device(self, kernel, method):
-        return (self._dense().device.type == 'cuda'
-                and not self.kernel_options and hasattr(kernel, method))
+    def _device(self, kernel, method, *args, **kwargs):
+        """The result of the kernel's device method, or None where the
+        model or the kernel has no device path."""
+        if not on_device(self._dense(), self.kernel_options):
+            return None
+        return device_call(kernel, method, *args, **kwargs)
 
     def _cross(self, kernel, X, Y, jac=False):
         """``kernel(X, Y)`` as a float64 tensor (and its gradient as a
         `LazyGradient` over the columns the kernel hands over)."""
         torch = _torch()
         la = self._dense()
-        if self._on_device(kernel, 'device_cross_gram'):
-            try:
-                out = kernel.device_cross_gram(X, Y, eval_gradient=jac)
-            except TypeError:        # not the HIP backend, or pair-sharded
-                out = None
-            if out is not None:
-                K, dK = out if jac else (out, None)
-                K = torch.as_tensor(K, device=la.device).to(torch.float64)
-                if dK is not None:
-                    from ...kernel.fix import LazyGradient
-                    if not isinstance(dK, LazyGradient):
-                        dK = LazyGradient(torch.as_tensor(dK,
-                                                          device=la.device))
-                return (K, dK) if jac else K
+        out = self._device(kernel, 'device_cross_gram', X, Y,
+                           eval_gradient=jac)
+        if out is not None:
+            K, dK = out if jac else (out, None)
+            K = as_float64(K, la.device)
+            if dK is not None:
+                from ...kernel.fix import LazyGradient
+                if not isinstance(dK, LazyGradient):
+                    dK = LazyGradient(torch.as_tensor(dK, device=la.device))
+            return (K, dK) if jac else K
         if jac:
             K, dK = kernel(X, Y, eval_gradient=True, **self.kernel_options)
             return la.tensor(K), _lazy(la.tensor(dK))
@@ -164,15 +148,10 @@ class LowRankApproximateGPR:
         tensor of its own (and its gradient as a `LazyGradient`)."""
         torch = _torch()
         la = self._dense()
-        out = None
-        if self._on_device(kernel, 'device_gram'):
-            try:
-                out = kernel.device_gram(C, eval_gradient=jac)
-            except TypeError:
-                out = None
+        out = self._device(kernel, 'device_gram', C, eval_gradient=jac)
         if out is not None:
             K, dK = out if jac else (out, None)
-            K = torch.as_tensor(K, device=la.device).to(torch.float64).clone()
+            K = as_float64(K, la.device).clone()
             if dK is not None:
                 # (the graph kernel's views of device_gram are only valid
                 # until its next evaluation: the planes are copied, m x m x n)
@@ -192,33 +171,23 @@ class LowRankApproximateGPR:
 
     def _prior_diag(self, Z):
         """``kernel.diag(Z)``, regularised, as a float64 tensor."""
-        torch = _torch()
         la = self._dense()
-        if self._on_device(self.kernel, 'device_diag'):
-            try:
-                d = self.kernel.device_diag(Z)
-                return self._regularize(
-                    torch.as_tensor(d, device=la.device).to(torch.float64),
-                    self.alpha)
-            except TypeError:
-                pass
+        d = self._device(self.kernel, 'device_diag', Z)
+        if d is not None:
+            return self._regularize(as_float64(d, la.device), self.alpha)
         return self._regularize(
             la.tensor(self.kernel.diag(Z, **self.kernel_options)), self.alpha)
 
     def _prior_gram(self, Z):
         torch = _torch()
         la = self._dense()
-        if self._on_device(self.kernel, 'device_gram'):
-            try:
-                K = torch.as_tensor(self.kernel.device_gram(Z),
-                                    device=la.device).to(torch.float64)
-                K = K.clone()
-                torch.cuda.current_stream(la.device).synchronize()
-                diag = torch.diagonal(K)
-                diag.copy_(self._regularize(diag, self.alpha))
-                return K
-            except TypeError:
-                pass
+        K = self._device(self.kernel, 'device_gram', Z)
+        if K is not None:
+            K = as_float64(K, la.device).clone()
+            torch.cuda.current_stream(la.device).synchronize()
+            diag = torch.diagonal(K)
+            diag.copy_(self._regularize(diag, self.alpha))
+            return K
         K = np.array(self.kernel(Z, **self.kernel_options), dtype=np.float64)
         K.flat[::len(K) + 1] = self._regularize(K.flat[::len(K) + 1],
                                                 self.alpha)
@@ -264,28 +233,7 @@ class LowRankApproximateGPR:
                     'regressor.')
             else:
                 raise RuntimeError(f'Unknown loss function: {loss}.')
-            x0 = np.array(self.kernel.theta, dtype=float)
-            starts = [x0] + [x0 + theta_jitter * np.random.randn(len(x0))
-                             for _ in range(repeat - 1)]
-            best = None
-            for x in starts:
-                res = minimize(
-                    fun=lambda t: objective(t, eval_gradient=True,
-                                            clone_kernel=False,
-                                            verbose=verbose),
-                    method=self.optimizer, x0=x, bounds=self.kernel.bounds,
-                    jac=True, tol=tol)
-                if best is None or (res.success and res.fun < best.fun):
-                    best = res
-            if verbose:
-                print(f'Optimization result:\n{best}')
-            if not best.success:
-                raise RuntimeError(
-                    f'Training using the {loss} loss did not converge, got:\n'
-                    f'{best}')
-            self.kernel.theta = best.x
-            #: the optimiser's report (scipy OptimizeResult: nit, nfev, fun)
-            self.optimization_result = best
+            self._optimize(objective, loss, tol, repeat, theta_jitter, verbose)
         la = self._dense()
         self.Kcc_rsqrt = self._corespace(self._core(self.kernel, self._C))[0]
         Kxc = self._cross(self.kernel, self._X, self._C)
@@ -375,19 +323,9 @@ class LowRankApproximateGPR:
         constant) at the log-scale hyperparameters `theta`, and its gradient
         w.r.t. `theta`."""
         torch = _torch()
-        theta = np.array(theta if theta is not None else self.kernel.theta,
-                         dtype=float)
+        theta, X, y, y_mask, kernel = self._prologue(theta, X, y,
+                                                     clone_kernel)
         C = C if C is not None else self._C
-        X = X if X is not None else self._X
-        if y is not None:
-            y_mask, y = self.mask(y)
-        else:
-            y, y_mask = self._y, self._y_mask
-        if clone_kernel is True:
-            kernel = self.kernel.clone_with_theta(theta)
-        else:
-            kernel = self.kernel
-            kernel.theta = theta
         la = self._dense()
 
         t = time.perf_counter()
@@ -430,11 +368,7 @@ class LowRankApproximateGPR:
         grad = None
         if eval_gradient is True:
             d = packed[2:]
-            mask = np.asarray(getattr(kernel, 'active_theta_mask',
-                                      np.ones(len(d), dtype=bool)))
-            if len(d) == len(mask) and len(d) != len(theta):
-                d = d[mask]
-            grad = d * np.exp(theta)
+            grad = d[active_planes(kernel, len(d))] * np.exp(theta)
         t_linalg = time.perf_counter() - t
         if verbose:
             print(f'logP {value:12.5g}  y^T.K.y {yKy:12.5g}  '

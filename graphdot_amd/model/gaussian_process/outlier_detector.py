@@ -25,8 +25,11 @@ common path.  Masked targets (None / NaN) drop their rows and columns, and
 instead of crashing."""
 import time
 import numpy as np
-from scipy.optimize import minimize
-from .gpr import GaussianProcessRegressor, _torch
+from .._device_kernel import (device_call, on_device, as_float64,
+                              active_planes)
+from .._fit import multistart
+from ._base import GaussianProcessRegressorBase
+from .gpr import _torch
 
 
 class _Inverse:
@@ -59,7 +62,7 @@ class _Inverse:
                     and normK * normKinv < 1.0 / beta)
 
 
-class GPROutlierDetector:
+class GPROutlierDetector(GaussianProcessRegressorBase):
     """Gaussian process regression with per-sample noise (outlier) learning.
 
     Parameters
@@ -84,25 +87,9 @@ class GPROutlierDetector:
     def __init__(self, kernel, sigma_bounds=(1e-4, np.inf), beta=1e-8,
                  optimizer=True, normalize_y=False, kernel_options={},
                  device='auto'):
-        self.kernel = kernel
+        super().__init__(kernel, beta, optimizer, normalize_y, '+',
+                         kernel_options, device)
         self.sigma_bounds = sigma_bounds
-        self.beta = beta
-        self.optimizer = 'L-BFGS-B' if optimizer is True else optimizer
-        self.normalize_y = normalize_y
-        self.regularization = '+'
-        self.kernel_options = dict(kernel_options)
-        self.device = device
-
-    # the training data, masking, kernel matrices, dense algebra and
-    # persistence of GaussianProcessRegressor
-    X = GaussianProcessRegressor.X
-    y = GaussianProcessRegressor.y
-    mask = staticmethod(GaussianProcessRegressor.mask)
-    _regularize = GaussianProcessRegressor._regularize
-    _gramian = GaussianProcessRegressor._gramian
-    _dense = GaussianProcessRegressor._dense
-    save = GaussianProcessRegressor.save
-    load = GaussianProcessRegressor.load
 
     @property
     def y_uncertainty(self):
@@ -122,16 +109,14 @@ class GPROutlierDetector:
         """(Ks, planes, plane indices) as device tensors straight from the
         kernel's device buffers, or None where the kernel has no device path
         (the host path then runs the same algebra through torch)."""
-        if la.device.type != 'cuda' or self.kernel_options \
-                or not hasattr(kernel, 'device_gram'):
+        if not on_device(la, self.kernel_options):
             return None
         torch = _torch()
-        try:
-            out = kernel.device_gram(X, eval_gradient=jac)
-        except TypeError:            # not the HIP backend
+        out = device_call(kernel, 'device_gram', X, eval_gradient=jac)
+        if out is None:
             return None
         Kd, dKd = out if jac else (out, None)
-        Ks = torch.as_tensor(Kd, device=la.device).to(torch.float64).clone(
+        Ks = as_float64(Kd, la.device).clone(
             memory_format=torch.contiguous_format)
         if dKd is None:
             return Ks, None, np.zeros(0, dtype=np.int64)
@@ -139,10 +124,7 @@ class GPROutlierDetector:
         # graph kernel hands over all its columns, of which the active ones
         # are read
         P = torch.as_tensor(dKd, device=la.device)
-        mask = np.asarray(kernel.active_theta_mask)
-        planes = np.flatnonzero(mask) if P.shape[2] == len(mask) \
-            else np.arange(P.shape[2])
-        return Ks, P, planes
+        return Ks, P, active_planes(kernel, P.shape[2])
 
     def _evaluate(self, kernel, X, y, sigma2, jac):
         """(yKy, log|Ks|, d_theta (linear scale), d_alpha, Kinv, Ks) with
@@ -175,9 +157,7 @@ class GPROutlierDetector:
             timing[name] = time.perf_counter() - since
 
         if fused:
-            from . import _outlier
-            from ._potrf import (factor_inverse, parse_head, read_head,
-                                 cholesky_, FactorisationError)
+            from . import _outlier, _potrf
 
             def epi(Kinv):
                 return _outlier.epilogue(Kinv, Ks, yt, s2, P, planes)
@@ -185,16 +165,11 @@ class GPROutlierDetector:
             # ONE download: status, log-determinant shares and the packed
             # epilogue
             t0 = time.perf_counter()
-            Kinv, head, nb = factor_inverse(Ks)
-            blob = torch.cat((head[:16 + 2 * nb].view(torch.float64),
+            Kinv, head, nb = _potrf.factor_inverse(Ks)
+            blob = torch.cat((_potrf.packed_head(head, nb),
                               epi(Kinv))).cpu().numpy()
             tick('factor', t0)
-            completed, logdet = parse_head(blob[:8 + nb], nb)
-            if not completed:
-                raise FactorisationError(
-                    'spd_factor_invert_f64 gave up waiting for a tile')
-            logdet *= 2.0
-            out = blob[8 + nb:]
+            logdet, out = _potrf.logdet(blob, nb)
             path = None
             if np.isfinite(logdet):
                 if _Inverse.certified(out[1], out[2], beta):
@@ -203,8 +178,8 @@ class GPROutlierDetector:
                     t0 = time.perf_counter()
                     B = Ks.clone()
                     B.diagonal().sub_(beta * float(out[1]))
-                    L = cholesky_(B)
-                    if np.isfinite(read_head(L._gd_head, nb)[1]):
+                    L = _potrf.cholesky_(B)
+                    if np.isfinite(_potrf.read_head(L._gd_head, nb)[1]):
                         path = 'B'
                     tick('certificate_B', t0)
             if path is None:
@@ -242,23 +217,14 @@ class GPROutlierDetector:
         return (yKy, logdet, out[3:3 + nt], out[3 + nt:3 + nt + n], Kinv,
                 Ks)
 
-    def _inputs(self, X, y):
-        """(kept X, kept y) of explicit arguments or of the training set."""
-        if y is not None:
-            m, y = self.mask(y)
-            X = self._kept(X if X is not None else self._X, m)
-        else:
-            y = self._y
-            X = self._kept(X if X is not None else self._X, self._y_mask)
-        return X, y
-
     def log_marginal_likelihood(self, theta_ext, X=None, y=None,
                                 eval_gradient=False, clone_kernel=True,
                                 verbose=False):
         """``y^T K^-1 y + log|K|`` at the log-scale kernel hyperparameters
         followed by ``log sigma`` per (kept) sample, and its gradient
         w.r.t. them."""
-        X, y = self._inputs(X, y)
+        X, y, y_mask = self._targets(X, y)
+        X = self._kept(X, y_mask)
         theta_ext = np.asarray(theta_ext, dtype=float)
         nt = len(self.kernel.theta)
         if len(theta_ext) != nt + len(y):
@@ -267,11 +233,7 @@ class GPROutlierDetector:
                 f'levels expected, got {len(theta_ext)} values')
         theta, log_sigma = theta_ext[:nt], theta_ext[nt:]
         sigma = np.exp(log_sigma)
-        if clone_kernel is True:
-            kernel = self.kernel.clone_with_theta(theta)
-        else:
-            kernel = self.kernel
-            kernel.theta = theta
+        kernel = self._kernel_at(theta, clone_kernel)
         yKy, logdet, d_theta, d_alpha, *_ = self._evaluate(
             kernel, X, y, sigma**2, eval_gradient is True)
         value = yKy + logdet
@@ -325,13 +287,10 @@ class GPROutlierDetector:
 
         bounds = np.vstack((np.asarray(self.kernel.bounds, dtype=float),
                             np.tile(np.log(self.sigma_bounds), (N, 1))))
-        opt = None
-        for x in xgen(repeat):
-            res = minimize(fun=objective, method=self.optimizer,
-                           x0=np.concatenate((x, np.log(udist(N)))),
-                           bounds=bounds, jac=True, tol=tol)
-            if opt is None or (res.success and res.fun < opt.fun):
-                opt = res
+        opt = multistart(
+            objective,
+            (np.concatenate((x, np.log(udist(N)))) for x in xgen(repeat)),
+            self.optimizer, bounds, tol)
         if verbose:
             print(f'Optimization result:\n{opt}')
         if not opt.success:
