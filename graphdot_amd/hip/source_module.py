@@ -82,6 +82,7 @@ STATIC_SOURCES = (
     'model/gaussian_field/field.hip',
     'model/gaussian_process/outlier.hip',
     'model/gaussian_process/posterior.hip',
+    'model/gaussian_process/laplace.hip',
 )
 #: file name -> SourceModule
 STATIC = {os.path.basename(p): SourceModule(os.path.join(_PACKAGE, p))

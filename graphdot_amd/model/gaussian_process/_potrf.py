@@ -93,7 +93,18 @@ def factor_inverse(K):
     assert K.is_cuda and K.dtype == torch.float64 and K.dim() == 2
     n = K.shape[0]
     assert K.shape[1] == n and n >= 1
-    A = K.clone(memory_format=torch.contiguous_format)
+    return factor_inverse_(K.clone(memory_format=torch.contiguous_format))
+
+
+def factor_inverse_(A):
+    """`factor_inverse` of a matrix the caller has no further use for: the
+    factor is computed in the memory of the row-major contiguous `A` (L in
+    its lower tiles afterwards) instead of in a copy."""
+    import torch
+    assert A.is_cuda and A.dtype == torch.float64 and A.dim() == 2
+    n = A.shape[0]
+    assert A.shape[1] == n and n >= 1
+    assert n == 1 or A.stride() == (n, 1)
     Kinv, head = _dataflow(A, True)
     return Kinv, head, -(-n // _B)
 
