@@ -25,6 +25,9 @@ struct nz_t {            // one directed nonzero of the adjacency matrix
 };
 
 struct graph_header_t {  // 64 bytes, see _devicegraph.HEADER_DTYPE
+    // (quotient images, _devicegraph.quotient_graph: the node count of the
+    // quotient in the low half, that of the full graph in the high half --
+    // both fit 16 bits; full images leave the high half 0)
     std::int32_t n_node;
     std::int32_t n_nz;   // directed nonzeros (self loop counted once)
     std::uint32_t degree, node, rowptr, nz, edge, perm;  // byte offsets
@@ -45,6 +48,14 @@ template<class Node, class Edge> struct graph_t {
     nz_t const *nz;                // [n_nz] CSR order
     edge_t const *edge;            // [n_nz] AoS edge labels (incl. weight)
     std::uint16_t const *perm;     // [n_node] new id -> caller's node id
+    // Quotient images only: the twin leaves of a node (equal records, one
+    // shared neighbour) are merged into one representative of multiplicity m.
+    // `scale` = sqrt(m) per node, a section of doubles between the degrees
+    // and the node records (a float sqrt(2) would cap a double solve at
+    // 6e-8); `n_orig` = nodes of the full graph.  `degree` keeps the degrees
+    // of the full graph.
+    double const *scale = nullptr; // [n_node]
+    int n_orig = 0;
 
     __device__ __forceinline__ graph_t(char const *arena, graph_header_t const &h)
         : n_node(h.n_node), n_nz(h.n_nz),
@@ -54,6 +65,14 @@ template<class Node, class Edge> struct graph_t {
           nz(reinterpret_cast<nz_t const *>(arena + h.nz)),
           edge(reinterpret_cast<edge_t const *>(arena + h.edge)),
           perm(reinterpret_cast<std::uint16_t const *>(arena + h.perm)) {}
+
+    // the view of a quotient image (`h`: its header with the plain node count)
+    __device__ static __forceinline__ graph_t quotient(char const *arena, graph_header_t const &h, int n_orig_) {
+        graph_t g(arena, h);
+        g.scale = reinterpret_cast<double const *>(arena + h.degree + ((4u * (unsigned)h.n_node + 15u) & ~15u));
+        g.n_orig = n_orig_;
+        return g;
+    }
 };
 
 }  // namespace graphdot

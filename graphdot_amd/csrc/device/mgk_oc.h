@@ -237,9 +237,22 @@ template<class K> struct packed_edge<K, std::void_t<typename K::packed_edge_t>> 
     using type = typename K::packed_edge_t;
 };
 
-template<class real, int S, int R, int W, int C, bool NODAL, int DMAX, bool TAB, bool NGRAD, int MAXIMIN, class LAY, class Graph, class NodeK, class EdgeK, class PStart>
+// QUOT: the pair is solved on the twin-leaf QUOTIENT images of its graphs
+// (_devicegraph.quotient_graph).  Leaves that are exact
+// copies of a sibling -- the hydrogens of a CH3 group -- carry equal entries in
+// every CG vector; one representative of multiplicity m stands for them, and
+// with every vector rescaled by s = sqrt(m) the quotient system is symmetric
+// again: off-diagonal entries times s(i) s(j) per graph, right-hand side and
+// starting probability times s(i1) s(i2), diagonal (full-graph degrees, node
+// kernel) as it was.  The rescaled vectors have the inner products of the full
+// ones, so alpha, beta, rTr and K are those of the full system to rounding;
+// the stopping rule and the iteration cap count the rows of the FULL pair.
+// All of it is set-up: the CG loop is the one of the full images.
+template<class real, int S, int R, int W, int C, bool NODAL, int DMAX, bool TAB, bool NGRAD, int MAXIMIN, class LAY, class Graph, class NodeK, class EdgeK, class PStart, bool QUOT = false>
 struct oc_solver {
     constexpr static bool STATIC = LAY::is_static;
+    static_assert(!QUOT || (C == 1 && !NODAL && !NGRAD && !MAXIMIN && S > 0),
+                  "quotient images: graph-level values of the slot solvers");
     // (Round 6, measured and dropped: static layouts of SEVERAL waves per pair
     // for graphs of degree 5-8 -- one compile-time layout per workgroup that
     // dominates the trip profile of each of its waves.  Configuration 2's
@@ -504,6 +517,23 @@ struct oc_solver {
         return out;
     }
 
+    // header of a graph; QUOT: the node count of the full graph (high half of
+    // n_node, graph.h) goes to `n_orig`, the header keeps the quotient's
+    __device__ static __forceinline__ graph_header_t load_header(graph_header_t const *ptr, [[maybe_unused]] int &n_orig) {
+        if constexpr (QUOT) {
+            graph_header_t h = scalar_load(ptr);
+            n_orig = (int)((unsigned)h.n_node >> 16);
+            h.n_node &= 0xFFFF;
+            return h;
+        } else {
+            return scalar_load(ptr);
+        }
+    }
+    __device__ static __forceinline__ Graph view_graph(char const *image, graph_header_t const &h, [[maybe_unused]] int n_orig) {
+        if constexpr (QUOT) return Graph::quotient(image, h, n_orig);
+        else return Graph(image, h);
+    }
+
     // alpha and beta of the CG recurrence, a / b of two wave-uniform numbers.
     // Double: v_rcp_f64 and two Newton steps, then one product -- 6
     // instructions for a result within 1.5 ulp, against the 9 to 11 of the
@@ -532,6 +562,7 @@ struct oc_solver {
         int i1, i2, rs1, rs2, d1, d2, prod;
     };
     constexpr static int GD_ = G0 ? DMAX : 1;
+    constexpr static int GQ_ = QUOT ? GD_ : 1;
     struct grid_t {       // GRID: the first batch's row as 2 DMAX half-terms
         unsigned a[GD_], b[GD_];      // element indices (clamped into the row)
         unsigned j1[GD_], j2[GD_];    // lp byte address = j1[u] + j2[v]
@@ -574,7 +605,8 @@ struct oc_solver {
         }
         for (unsigned t = blockIdx.x; t < prm.n_launch_jobs; t += gridDim.x) {
             const job_t job = scalar_load(prm.jobs + t);
-            const graph_header_t h1 = scalar_load(headers + job.i), h2 = scalar_load(headers + job.j);
+            [[maybe_unused]] int no1 = 0, no2 = 0;     // QUOT: nodes of the full graphs
+            const graph_header_t h1 = load_header(headers + job.i, no1), h2 = load_header(headers + job.j, no2);
             const int n1 = h1.n_node, n2 = h2.n_node, N = n1 * n2;
             const int ldp = n2 | 1;            // odd row stride of p: banks spread
             const real q = prm.q, q0 = prm.q0;
@@ -623,8 +655,12 @@ struct oc_solver {
                         for (int c = 0; c < C; ++c) lY[(k * T + tid) * C + c] = 0;
                 }
             }
-            const Graph g1(lG1 + cb1 - h1.degree, h1);
-            const Graph g2(lG2 + cb2 - h2.degree, h2);
+            const Graph g1 = view_graph(lG1 + cb1 - h1.degree, h1, no1);
+            const Graph g2 = view_graph(lG2 + cb2 - h2.degree, h2, no2);
+            // QUOT: s(i) s(j) of nonzero z of graph g
+            [[maybe_unused]] auto qweight = [](Graph const &g, nz_t z) -> real {
+                return real(at32(g.scale, (unsigned)z.i)) * real(at32(g.scale, (unsigned)z.j));
+            };
             std::uint8_t const *const ncls1 = reinterpret_cast<std::uint8_t const *>(lG1);
             std::uint8_t const *const ncls2 = reinterpret_cast<std::uint8_t const *>(lG2);
             std::uint8_t const *const ecls1 = ncls1 + nzpad1;
@@ -873,8 +909,16 @@ struct oc_solver {
                     walk_t cur = G0 ? walk_t{} : open_walk(0);
                     [[maybe_unused]] grid_t grid;
                     [[maybe_unused]] edge_t ge1[GD_], ge2[GD_];
+                    [[maybe_unused]] real gw1[GQ_], gw2[GQ_];     // QUOT: s(i) s(j) of the half-terms
                     if constexpr (G0 > 0) {
                         grid = open_grid(lp_off, ELEM);
+                        if constexpr (QUOT) {
+#pragma unroll
+                            for (int k = 0; k < GD_; ++k) {
+                                gw1[k] = qweight(g1, at32(g1.nz, grid.a[k]));
+                                gw2[k] = qweight(g2, at32(g2.nz, grid.b[k]));
+                            }
+                        }
                         if constexpr (!TAB || (GD_WEIGHTED && edge_weight<edge_t>::value)) {
 #pragma unroll
                             for (int k = 0; k < GD_; ++k) {
@@ -902,6 +946,7 @@ struct oc_solver {
                             } else {
                                 e = prm.edge_kernel(ge1[gu], ge2[gv]);
                             }
+                            if constexpr (QUOT) e *= gw1[gu] * gw2[gv];
                             // (slots without a term gather p[0] like the running
                             // walk's: lanes on one address share the LDS access,
                             // clamped neighbours would add bank conflicts -- 3.43
@@ -920,6 +965,7 @@ struct oc_solver {
                             const edge_t e1 = at32(g1.edge, a), e2 = at32(g2.edge, b);
                             e = prm.edge_kernel(e1, e2);
                         }
+                        if constexpr (QUOT) e *= qweight(g1, z1) * qweight(g2, z2);
                         col = ok ? __umul24((unsigned)z1.j, (unsigned)ldp) + (unsigned)z2.j : 0u;
                         col = lp_off + col * ELEM;
                         }
@@ -995,6 +1041,7 @@ struct oc_solver {
                             const edge_t e1 = at32(g1.edge, a), e2 = at32(g2.edge, b);
                             e = prm.edge_kernel(e1, e2);
                         }
+                        if constexpr (QUOT) e *= qweight(g1, z1) * qweight(g2, z2);
                         unsigned col = ok ? __umul24((unsigned)z1.j, (unsigned)ldp) + (unsigned)z2.j : 0u;
                         col = lp_off + col * ELEM;
                         if (SL > 0 && s >= SREG) {
@@ -1248,10 +1295,16 @@ struct oc_solver {
                     lY[(R + k) * T + tid] = mi[k];
                 }
                 paddr[k] = ok ? (int)__umul24((unsigned)i1, (unsigned)ldp) + i2 : dump;
-                const real b = ok ? dx * bscale : real(0);
+                real b = ok ? dx * bscale : real(0);
                 if constexpr (SEQ) xq[k] = 0;
                 else if constexpr (KEEP_X) x[0][k] = 0;
                 else pp[k] = real(prm.p_start(v1)) * real(prm.p_start(v2));
+                if constexpr (QUOT) {
+                    // the rescaled right-hand side and starting probability
+                    const real sc = real(at32(g1.scale, (unsigned)i1)) * real(at32(g2.scale, (unsigned)i2));
+                    b *= sc;
+                    pp[k] *= sc;
+                }
                 if constexpr (LEAN) {
                     const real zero[C] = {};
                     store_elem<C>(lY, k * T + tid, zero);
@@ -1290,7 +1343,7 @@ struct oc_solver {
                         }
                     }
                 }
-                const real tol = (C == 2) ? real(1e-10) * real(2 * N) : prm.ftol * real(N);
+                const real tol = (C == 2) ? real(1e-10) * real(2 * N) : prm.ftol * real(QUOT ? no1 * no2 : N);
                 // SEQ: the stacked rule rTr_0 + rTr_1 < tol^2 -- half the budget
                 // for the first system, what it left for the second
                 sreal tol2 = (sreal)(tol * tol);
@@ -1322,7 +1375,9 @@ struct oc_solver {
                 // iterations are used up: K of two one-node graphs came out as
                 // float(4/3) (scripts/fuzz_parity.py, seeds 4-6).  The double
                 // build iterates on to its tolerance: one or two more steps.)
-                const unsigned max_its = FSCAL ? 2u * (unsigned)N + 16u : (unsigned)N;
+                // (QUOT: the rows of the full pair, like the stopping rule)
+                const unsigned N_cap = (unsigned)(QUOT ? no1 * no2 : N);
+                const unsigned max_its = FSCAL ? 2u * N_cap + 16u : N_cap;
                 for (; its < max_its && rTz_s != sreal(0); ++its) {
                     job_sync<W>();   // p published
                     // row sums: sum over the slots of a batch, flushed to the

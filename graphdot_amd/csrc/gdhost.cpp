@@ -7,12 +7,14 @@
 // function here reproduces their results byte for byte (tests/test_host_model
 // .py, tests/test_abi_and_host_logic.py).
 #include "gdhost.h"
+#include "gdquotient.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <atomic>
+#include <cmath>
 #include <exception>
 #include <mutex>
 #include <thread>
@@ -286,6 +288,92 @@ int gdh_pack_graphs(int32_t G, const int64_t *node_off, const int64_t *edge_off,
     });
     return 0;
 } catch (...) { return -3; }   // (bad_alloc, system_error: never across the C ABI)
+
+int gdh_quotient_graph(int32_t n, int32_t nnz, const float *degree,
+                       const uint8_t *node, int32_t node_size, const uint16_t *rowptr,
+                       const uint16_t *nz, const uint8_t *edge, int32_t edge_size,
+                       const uint16_t *perm, uint8_t *blob, int64_t capacity,
+                       int64_t *sec_off, int64_t *counts) try {
+    if (n < 0 || nnz < 0 || node_size < 0 || edge_size < 0) return -1;
+    for (int32_t i = 0; i < n; ++i)
+        if (rowptr[i + 1] < rowptr[i] || rowptr[i + 1] > nnz) return -1;
+    for (int32_t e = 0; e < nnz; ++e)
+        if (nz[2 * e] >= n || nz[2 * e + 1] >= n) return -1;
+    // ---- twin groups: the first member represents its group ----------------
+    std::vector<int32_t> mult((size_t)n, 1), reps;
+    std::vector<char> drop((size_t)n, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        if (rowptr[i + 1] - rowptr[i] != 1) continue;
+        const int32_t e = rowptr[i], par = nz[2 * e + 1];
+        if (par == i || rowptr[par + 1] - rowptr[par] < 2) continue;
+        bool merged = false;
+        for (int32_t r : reps) {
+            const int32_t er = rowptr[r];
+            if (nz[2 * er + 1] == par &&
+                std::memcmp(node + (size_t)r * node_size, node + (size_t)i * node_size, (size_t)node_size) == 0 &&
+                std::memcmp(edge + (size_t)er * edge_size, edge + (size_t)e * edge_size, (size_t)edge_size) == 0) {
+                ++mult[(size_t)r];
+                drop[(size_t)i] = 1;
+                merged = true;
+                break;
+            }
+        }
+        if (!merged) reps.push_back(i);
+    }
+    // ---- adjacency counts of the quotient, renumbering (stable) ------------
+    std::vector<int32_t> cnt((size_t)n, 0), order, rank((size_t)n, -1);
+    for (int32_t e = 0; e < nnz; ++e)
+        if (!drop[nz[2 * e]] && !drop[nz[2 * e + 1]]) ++cnt[nz[2 * e]];
+    for (int32_t i = 0; i < n; ++i)
+        if (!drop[(size_t)i]) order.push_back(i);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t x, int32_t y) { return cnt[(size_t)x] > cnt[(size_t)y]; });
+    const int64_t nq = (int64_t)order.size();
+    for (int64_t k = 0; k < nq; ++k) rank[(size_t)order[(size_t)k]] = (int32_t)k;
+    struct qnz_t {
+        int32_t i, j, e;
+    };
+    std::vector<qnz_t> q;
+    for (int32_t e = 0; e < nnz; ++e)
+        if (!drop[nz[2 * e]] && !drop[nz[2 * e + 1]])
+            q.push_back({rank[nz[2 * e]], rank[nz[2 * e + 1]], e});
+    std::sort(q.begin(), q.end(), [](qnz_t const &x, qnz_t const &y) {
+        return x.i != y.i ? x.i < y.i : x.j < y.j;
+    });
+    const int64_t nnzq = (int64_t)q.size();
+    // ---- sections -----------------------------------------------------------
+    const int64_t sizes[7] = {4 * nq, 8 * nq, (int64_t)node_size * nq, 2 * (nq + 1),
+                              4 * nnzq, (int64_t)edge_size * nnzq, 2 * nq};
+    int64_t c = 0;
+    for (int s_ = 0; s_ < 7; ++s_) {
+        sec_off[s_] = c;
+        c += pad(sizes[s_]);
+    }
+    c = std::max<int64_t>(c, ALIGN);
+    if (c > capacity) return -2;
+    std::memset(blob, 0, (size_t)c);
+    uint16_t *rp = reinterpret_cast<uint16_t *>(blob + sec_off[3]);
+    rp[0] = 0;
+    for (int64_t k = 0; k < nq; ++k) {
+        const int32_t old = order[(size_t)k];
+        const float d = degree[old];
+        const double sc = std::sqrt((double)mult[(size_t)old]);
+        std::memcpy(blob + sec_off[0] + 4 * k, &d, 4);
+        std::memcpy(blob + sec_off[1] + 8 * k, &sc, 8);
+        std::memcpy(blob + sec_off[2] + k * node_size, node + (size_t)old * node_size, (size_t)node_size);
+        rp[k + 1] = (uint16_t)(rp[k] + cnt[(size_t)old]);
+        std::memcpy(blob + sec_off[6] + 2 * k, perm + old, 2);
+    }
+    for (int64_t k = 0; k < nnzq; ++k) {
+        const uint16_t ij[2] = {(uint16_t)q[(size_t)k].i, (uint16_t)q[(size_t)k].j};
+        std::memcpy(blob + sec_off[4] + 4 * k, ij, 4);
+        std::memcpy(blob + sec_off[5] + k * edge_size, edge + (size_t)q[(size_t)k].e * edge_size, (size_t)edge_size);
+    }
+    counts[0] = nq;
+    counts[1] = nnzq;
+    counts[2] = c;
+    return 0;
+} catch (...) { return -3; }
 
 int gdh_number_records(const uint8_t *rec, int64_t n, int32_t itemsize,
                        const int32_t *part_off, const int32_t *part_len,

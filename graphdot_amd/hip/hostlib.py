@@ -32,6 +32,8 @@ SIGNATURES = {
     'gdh_pairwise_jobs': [_i64, _i64, _vp],
     'gdh_gather_section': [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64],
     'gdh_assemble_arena': [_i64] + [_vp] * 9 + [_i64],
+    'gdh_quotient_graph': [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32,
+                           _vp, _vp, _i64, _vp, _vp],
 }
 
 
@@ -42,10 +44,10 @@ class HostLibError(RuntimeError):
 def build_library(force=False):
     """g++ csrc/gdhost.cpp -> csrc/libgdhost.so."""
     src = os.path.join(CSRC, 'gdhost.cpp')
-    hdr = os.path.join(INCLUDE, 'gdhost.h')
+    hdrs = [os.path.join(INCLUDE, h) for h in ('gdhost.h', 'gdquotient.h')]
     if (not force and os.path.exists(LIB_PATH)
-            and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(src),
-                                                  os.path.getmtime(hdr))):
+            and os.path.getmtime(LIB_PATH) >= max(
+                os.path.getmtime(f) for f in [src] + hdrs)):
         return LIB_PATH
     cxx = os.environ.get('CXX', 'g++')
     tmp = LIB_PATH + f'.{os.getpid()}.tmp'
@@ -254,6 +256,27 @@ def assemble_arena(blob, blob_off, starts, cbytes, n_node, n_nz, ncls, ecls,
         None if ncls is None else _p(_c(ncls, np.uint8)),
         None if ecls is None else _p(_c(ecls, np.uint8)),
         _p(host), host.nbytes), 'gdh_assemble_arena')
+
+
+def quotient_graph(dg):
+    """gdh_quotient_graph on the image of the packed graph `dg`: (blob,
+    section offsets [7], nodes, nonzeros) of its twin-leaf quotient."""
+    n, nnz = int(dg.n_node), int(dg.n_nz)
+    nsz, esz = np.dtype(dg.node_t).itemsize, np.dtype(dg.edge_t).itemsize
+    o, src = dg.offsets, np.ascontiguousarray(dg.blob)
+    base = src.ctypes.data
+
+    def at(name):
+        return ctypes.c_void_p(base + int(o[name]))
+    cap = len(src) + 8 * n + 64
+    blob = np.empty(cap, np.uint8)
+    offs = np.zeros(7, np.int64)
+    counts = np.zeros(3, np.int64)
+    _check(lib().gdh_quotient_graph(
+        n, nnz, at('degree'), at('node'), nsz, at('rowptr'), at('nz'),
+        at('edge'), esz, at('perm'), _p(blob), cap, _p(offs), _p(counts)),
+        'gdh_quotient_graph')
+    return blob[:int(counts[2])], offs.tolist(), int(counts[0]), int(counts[1])
 
 
 # --------------------------------------------------------------------------

@@ -26,7 +26,8 @@ from ...microkernel import TensorProduct, Product
 from ...util.iterable import flatten, fold_like
 from ._backend import Backend
 from ._devicegraph import (DeviceGraph, GraphArena, HIST_BINS, class_bytes,
-                           degree_histograms, graph_features, pack_many)
+                           degree_histograms, graph_features, pack_many,
+                           quotient_graph)
 
 _TEMPLATE = os.path.join(os.path.dirname(__file__), 'template.hip')
 
@@ -538,6 +539,9 @@ class HIPBackend(Backend):
         Nodal Jacobians inside the launch (default) or by re-launches.
     native: bool
         Host side of a call in C++ (libgdhost.so, default) or in numpy.
+    quotient: bool
+        Plain graph-level value calls solve every pair on the twin-leaf
+        quotient images of its graphs (default; also ``$GD_QUOTIENT=0``: off).
     """
 
     @staticmethod
@@ -603,6 +607,8 @@ class HIPBackend(Backend):
         # the numpy restatements it is tested against
         self.native = bool(kwargs.pop(
             'native', True))
+        self.quotient = bool(kwargs.pop(
+            'quotient', os.environ.get('GD_QUOTIENT', '1') != '0'))
         if self.native:
             from ...hip import hostlib
             hostlib.lib()                  # fail loudly if it cannot be built
@@ -859,7 +865,7 @@ struct ${name}_t : ${name}_theta_t {
         ], align=True)
 
     def kernel_name(self, v, C, nodal=False, tab=False, ngrad=False,
-                    maximin=False):
+                    maximin=False, quot=False):
         """Entry point name: arithmetic, solver variant, flavour."""
         f = 'f64' if np.dtype(self.real) == np.float64 else 'f32'
         if v == GENERAL:
@@ -875,7 +881,8 @@ struct ${name}_t : ${name}_theta_t {
                 ('_L' + 'x'.join(map(str, v.L)) if v.L else '') + \
                 ('_nodal' if nodal else '') + ('_tab' if tab else '') + \
                 ('_ngrad' if ngrad else '') + (
-                    '_m3' if maximin == 2 else '_maximin' if maximin else '')
+                    '_m3' if maximin == 2 else '_maximin' if maximin else '') \
+                + ('_quot' if quot else '')
         return f'mgk_{f}_W{v.W}_S{v.S}_R{v.R}_C{C}' + \
             ('_nodal' if nodal else '') + ('_tab' if tab else '')
 
@@ -1043,7 +1050,7 @@ struct ${name}_t : ${name}_theta_t {
         return 1
 
     def _entry_point(self, v, C, nodal=False, tab=False, ngrad=False,
-                     maximin=False):
+                     maximin=False, quot=False):
         if v == TABLES:
             return Template(r'''
 extern "C" __global__ __launch_bounds__(256)
@@ -1058,14 +1065,15 @@ __attribute__((amdgpu_waves_per_eu(${waves})))
 void ${name}(${params} prm) {
     using solver = graphdot::mgk::oc_solver<real_t, ${S}, ${R}, ${W}, ${C},
         ${nodal}, ${D}, ${tab}, ${ngrad}, ${maximin}, ${layout}, graph_t,
-        node_kernel_t, edge_kernel_t, p_start_t>;
+        node_kernel_t, edge_kernel_t, p_start_t${quot}>;
     static_assert(solver::DLDS == ${dlds}, "Jacobi diagonals in LDS: the host sized the [Y] region for the other answer (HIPBackend.diagonals_in_lds)");
     __shared__ typename solver::lds_t lds;
     extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
     solver::run(prm, lds, reinterpret_cast<real_t *>(dyn_lds));
 }
 ''').render(threads=64 * v.W,
-            name=self.kernel_name(v, C, nodal, tab, ngrad, maximin),
+            name=self.kernel_name(v, C, nodal, tab, ngrad, maximin, quot),
+            quot=', true' if quot else '',
             dlds='true' if self.diagonals_in_lds(v, C, nodal or ngrad
                                                  or bool(maximin)) else 'false',
             maximin='2' if maximin == 2 else 'true' if maximin else 'false',
@@ -1132,7 +1140,7 @@ void ${name}(params_t prm) {
 
     def render_source(self, node_kernel, edge_kernel, p, node_t, edge_t,
                       variants, C, nodal=False, tab=False, weighted=False,
-                      ngrad=False, maximin=False):
+                      ngrad=False, maximin=False, quot=False):
         """Full translation unit for the given solver variants."""
         pd = self._params_dtype(node_kernel, edge_kernel, p)
         pfd = self._params_fd_dtype(node_kernel, edge_kernel, p)
@@ -1160,8 +1168,9 @@ void ${name}(params_t prm) {
             node_size=np.dtype(node_t).itemsize,
             edge_size=max(np.dtype(edge_t).itemsize, 1),
             params_size=pd.itemsize, params_fd_size=pfd.itemsize,
-            entry_points=[self._entry_point(v, C, nodal, tab, ngrad, maximin)
-                          for v in variants] + [''],
+            entry_points=[self._entry_point(
+                v, C, nodal, tab, ngrad, maximin,
+                quot and isinstance(v, OCVariant)) for v in variants] + [''],
         )
 
     def _module(self, source):
@@ -1700,6 +1709,51 @@ void ${name}(params_t prm) {
             edge_kernel = TensorProduct(weight=Product(), label=edge_kernel)
         return dgraphs, edge_kernel, C, fields
 
+    def _quotient_graphs(self, graphs, dgraphs, traits, C, ngrad=False,
+                         maximin=False):
+        """The twin-leaf quotient images of the graphs of a call
+        (_devicegraph.quotient_graph), or None when the
+        call keeps the full images: anything but a plain graph-level value
+        call -- gradient, nodal, lmin = 1, a maximin / M3 epilogue --, a graph
+        with variable-length attributes, or no twin group in the whole call.
+        Decided from the traits and the graphs alone; a quotient is made once
+        per graph and kept in its cookie."""
+        if (not self.quotient or C != 1 or ngrad or maximin
+                or traits.nodal is not False
+                or traits.lmin != 0 or not len(dgraphs)):
+            return None
+        hit = getattr(dgraphs, 'quotient', False)
+        if hit is not False:
+            return hit
+        key = ('quotient', self.uuid.int, np.dtype(self.real).str)
+        out, merged = _DeviceGraphList(), 0
+        for g, dg in zip(graphs, dgraphs):
+            q = g.cookie.get(key) if hasattr(g.cookie, 'get') else None
+            if q is None or q.n_orig != dg.n_node:
+                q = quotient_graph(dg, native=self.native)
+                if q is None:
+                    out = None
+                    break
+                g.cookie[key] = q
+            merged += q.n_merged
+            out.append(q)
+        if out is not None and merged == 0:
+            out = None
+        if out is not None:
+            out.ids = tuple(map(id, out))
+        try:
+            dgraphs.quotient = out
+        except AttributeError:             # a plain list
+            pass
+        return out
+
+    @staticmethod
+    def _quotient_launches(launches):
+        """Do all launches of a layout of quotient images run on slot
+        variants of the owner-computes solver (mgk_oc.h QUOT)?"""
+        return all(isinstance(L['variant'], OCVariant) and L['variant'].S > 0
+                   for L in launches)
+
     def _partition(self, dgraphs, jobs, C, tab_bytes=0, gtab=False,
                    oc_only=False, merge_map=None, nodal=False, mfma=False):
         """Host half of a layout: solver variant per job, launch order (by
@@ -1942,7 +1996,8 @@ void ${name}(params_t prm) {
 
     @staticmethod
     def _code_signature(node_kernel, edge_kernel, p, dgraphs, C, nodal,
-                        tab=False, gtab=False, ngrad=False, maximin=False):
+                        tab=False, gtab=False, ngrad=False, maximin=False,
+                        quot=False):
         """What the generated code depends on: the microkernel expressions
         and record types (not the hyperparameter values), the graphs' record
         types and the output mode.  (The dtypes themselves, not their
@@ -1950,10 +2005,11 @@ void ${name}(params_t prm) {
         return (node_kernel.gen_expr('x1', 'x2')[0], np.dtype(node_kernel.dtype),
                 edge_kernel.gen_expr('x1', 'x2')[0], np.dtype(edge_kernel.dtype),
                 p.gen_expr()[0], np.dtype(p.dtype), dgraphs[0].signature,
-                C, nodal, tab, gtab, ngrad, maximin)
+                C, nodal, tab, gtab, ngrad, maximin, quot)
 
     def _sources(self, used, node_kernel, edge_kernel, p, dgraphs, C, nodal,
-                 tab=False, gtab=False, ngrad=False, maximin=False):
+                 tab=False, gtab=False, ngrad=False, maximin=False,
+                 quot=False):
         """One translation unit per solver variant in use (+ the one of the
         table kernel, key 'tables', when the owner-computes solvers read
         global tables).  The node / edge / start-probability code is shared
@@ -1961,7 +2017,7 @@ void ${name}(params_t prm) {
         # rendering is pure text work on hyperparameter-independent inputs:
         # memoised on the generated expressions and the record types
         sig = self._code_signature(node_kernel, edge_kernel, p, dgraphs, C,
-                                   nodal, tab, gtab, ngrad, maximin)
+                                   nodal, tab, gtab, ngrad, maximin, quot)
         out = {}
         todo = [(k, self.variants[k]) for k in used]
         if gtab and any(isinstance(v, OCVariant) for _, v in todo):
@@ -1981,7 +2037,8 @@ void ${name}(params_t prm) {
                     tab=gtab if isinstance(v, OCVariant)
                     else (tab and v not in (GENERAL, TABLES, STREAM, MFMA)),
                     weighted=dgraphs[0].weighted, ngrad=ngrad,
-                    maximin=maximin if isinstance(v, OCVariant) else False)
+                    maximin=maximin if isinstance(v, OCVariant) else False,
+                    quot=quot)
             out[k] = self._source_cache[key]
         return out
 
@@ -2001,16 +2058,25 @@ void ${name}(params_t prm) {
         edge_kernel_in = edge_kernel
         dgraphs, edge_kernel, C, fields = self._graphs_and_kernels(
             graphs, node_kernel, edge_kernel, traits, timer)
-        arena = self._host_arena(dgraphs, fields)
-        tab_bytes = self._table_bytes(arena)
-        gtab = self._global_tables(arena)
-        jobs, used, order_all, launches = self._partition(
-            dgraphs, jobs, C, tab_bytes, gtab,
-            nodal=traits.nodal is not False,
-            mfma=self._label_blind(edge_kernel_in))
+        jobs_in = jobs
+        for quot in (True, False):
+            dgs = self._quotient_graphs(graphs, dgraphs, traits, C) \
+                if quot else dgraphs
+            if dgs is None:
+                continue
+            arena = self._host_arena(dgs, fields)
+            tab_bytes = self._table_bytes(arena)
+            gtab = self._global_tables(arena)
+            jobs, used, order_all, launches = self._partition(
+                dgs, jobs_in, C, tab_bytes, gtab,
+                nodal=traits.nodal is not False,
+                mfma=self._label_blind(edge_kernel_in) and not quot)
+            if not quot or self._quotient_launches(launches):
+                break
+        dgraphs = dgs
         sources = self._sources(used, node_kernel, edge_kernel, p, dgraphs, C,
                                 traits.nodal is not False, tab_bytes > 0,
-                                gtab)
+                                gtab, quot=quot)
         return dgraphs, edge_kernel, jobs, C, used, order_all, launches, \
             sources
 
@@ -2089,7 +2155,7 @@ void ${name}(params_t prm) {
     def prepare(self, graphs, node_kernel, edge_kernel, p, q, eps, ftol, gtol,
                 jobs, starts, nX, nY, nJ, traits, timer=None, packed=False,
                 gramian_ptr=None, gradient_ptr=None, ngrad=False,
-                maximin=None, merge_map=None):
+                maximin=None, merge_map=None, quotient=None):
         """Upload graphs / jobs, generate + compile code, partition the jobs.
         Returns a Plan whose launches can be replayed.  `gramian_ptr` /
         `gradient_ptr` (device addresses) make the kernels write into
@@ -2101,7 +2167,12 @@ void ${name}(params_t prm) {
         maximin distance, its hotspot (and with `ngrad` its gradient) per
         pair instead of the nodal matrix (`maximin_distance`).  `merge_map`:
         {variant index: variant index} launch merging decided on a larger job
-        list that `jobs` is a shard of (instead of by this list's counts)."""
+        list that `jobs` is a shard of (instead of by this list's counts).
+        `quotient`: with a `merge_map`, the launch merging of the call on its
+        twin-leaf quotient images, decided on that larger list too
+        (`_sharded.measured_shard_plan`: which images and which solver a pair
+        runs on must not depend on the shard it falls into), or None: the
+        full images."""
         tic = timer.tic if timer else (lambda *_: None)
         toc = timer.toc if timer else (lambda *_: None)
         runtime.ensure_device(self.device)
@@ -2110,10 +2181,24 @@ void ${name}(params_t prm) {
             graphs, node_kernel, edge_kernel, traits, timer, ngrad)
         # epilogue flavour: 0 none, 1 maximin, 2 M3 (mgk_oc.h MAXIMIN)
         flavour = 0 if maximin is None else (2 if maximin.get('m3') else 1)
-        lay = self._layout(dgraphs, jobs, starts, C, fields, timer, ngrad,
-                           flavour, merge_map,
-                           nodal=traits.nodal is not False,
-                           mfma=self._label_blind(edge_kernel_in))
+        # plain value calls: the twin-leaf quotient images, when every pair
+        # of them runs on a slot variant of the owner-computes solver
+        lay, quot = None, False
+        qgraphs = self._quotient_graphs(graphs, dgraphs, traits, C, ngrad,
+                                        flavour) \
+            if merge_map is None or quotient is not None else None
+        if qgraphs is not None:
+            lay = self._layout(qgraphs, jobs, starts, C, fields, timer,
+                               merge_map=quotient, nodal=False, mfma=False)
+            if self._quotient_launches(lay.launches):
+                dgraphs, quot = qgraphs, True
+            else:
+                lay = None
+        if lay is None:
+            lay = self._layout(dgraphs, jobs, starts, C, fields, timer, ngrad,
+                               flavour, merge_map,
+                               nodal=traits.nodal is not False,
+                               mfma=self._label_blind(edge_kernel_in))
         tab = lay.tab_bytes > 0
 
         tic('code generation')
@@ -2123,7 +2208,7 @@ void ${name}(params_t prm) {
         # renders, hashes and looks up nothing
         mkey = (self._code_signature(node_kernel, edge_kernel, p, dgraphs, C,
                                      nodal, tab, lay.gtab, ngrad,
-                                     flavour), tuple(lay.used),
+                                     flavour, quot), tuple(lay.used),
                 tuple(self.hipcc_extra), self.tables,
                 None if self.occupancy is None
                 else tuple(sorted(self.occupancy.items())))
@@ -2131,7 +2216,7 @@ void ${name}(params_t prm) {
         if hit is None:
             sources = self._sources(lay.used, node_kernel, edge_kernel, p,
                                     dgraphs, C, nodal, tab, lay.gtab, ngrad,
-                                    flavour)
+                                    flavour, quot)
             toc('code generation')
             tic('JIT')
             missing = [s for s in sources.values()
@@ -2150,6 +2235,7 @@ void ${name}(params_t prm) {
         plan = Plan()
         plan.layout = lay
         plan.traits, plan.C, plan.n_jobs = traits, C, lay.n_jobs
+        plan.quotient = quot
         plan.nX, plan.nY, plan.nJ = int(nX), int(nY), int(nJ)
         plan.packed = packed
         plan.keep = (lay.arena, lay.arena_buf, dgraphs)
@@ -2185,7 +2271,7 @@ void ${name}(params_t prm) {
                 else tab and L['variant'] not in (GENERAL, STREAM, MFMA)
             L['fn'] = fn = L['module'].function(
                 self.kernel_name(L['variant'], C, nodal, L['tab'], ngrad,
-                                 flavour))
+                                 flavour, quot))
             if L['variant'] == STREAM:
                 # few pairs: several workgroups per pair, a cooperative
                 # launch (mgk_stream.h).  M = what the chip holds at once over

@@ -774,6 +774,129 @@ def pack_many_numpy(graphs, real=np.float32):
     return out
 
 
+#: sections of a quotient image, in blob order (`scale`: float64 sqrt(m))
+QUOTIENT_SECTIONS = ('degree', 'scale', 'node', 'rowptr', 'nz', 'edge', 'perm')
+
+
+def twin_groups(dg):
+    """Twin-leaf groups of a packed graph: (keep, mult) -- `keep` the nodes
+    (packed numbering, ascending) that stay in the quotient, `mult` their
+    multiplicities.  A twin group is a maximal set of m >= 2 nodes that have
+    exactly one neighbour each and no self loop, share that neighbour, which
+    itself has at least two neighbours (H-H is not merged), and whose packed
+    node records and edge records to the parent (weight included) are
+    bytewise equal; its first node represents it with multiplicity m."""
+    n = dg.n_node
+    node_t, edge_t = np.dtype(dg.node_t), np.dtype(dg.edge_t)
+    o = dg.offsets
+    nodes = dg.blob[o['node']:o['node'] + n * node_t.itemsize].reshape(
+        n, node_t.itemsize)
+    edges = dg.blob[o['edge']:o['edge'] + dg.n_nz * edge_t.itemsize].reshape(
+        dg.n_nz, edge_t.itemsize)
+    rowptr = np.asarray(dg.rowptr, dtype=np.int64)
+    nz_j = np.asarray(dg.nz['j'], dtype=np.int64)
+    cnt = np.diff(rowptr)
+    mult = np.ones(n, dtype=np.int64)
+    drop = np.zeros(n, dtype=bool)
+    reps = {}                          # (parent, node bytes, edge bytes) -> rep
+    for i in range(n):
+        if cnt[i] != 1:
+            continue
+        e = rowptr[i]
+        par = nz_j[e]
+        if par == i or cnt[par] < 2:
+            continue
+        key = (int(par), nodes[i].tobytes(), edges[e].tobytes())
+        rep = reps.setdefault(key, i)
+        if rep != i:
+            drop[i] = True
+            mult[rep] += 1
+    keep = np.flatnonzero(~drop)
+    return keep, mult[keep]
+
+
+def _quotient_blob_numpy(dg):
+    """(blob, section offsets [7], n, nnz) of the quotient image of `dg`: the
+    specification `gdh_quotient_graph` is held to byte for byte."""
+    n = dg.n_node
+    node_t, edge_t = np.dtype(dg.node_t), np.dtype(dg.edge_t)
+    o = dg.offsets
+    nodes = dg.blob[o['node']:o['node'] + n * node_t.itemsize].reshape(
+        n, node_t.itemsize)
+    edges = dg.blob[o['edge']:o['edge'] + dg.n_nz * edge_t.itemsize].reshape(
+        dg.n_nz, edge_t.itemsize)
+    keep, mult = twin_groups(dg)
+    kept = np.zeros(n, dtype=bool)
+    kept[keep] = True
+    zi = np.asarray(dg.nz['i'], dtype=np.int64)
+    zj = np.asarray(dg.nz['j'], dtype=np.int64)
+    zsel = np.flatnonzero(kept[zi] & kept[zj])          # CSR order of the full graph
+    cnt = np.bincount(zi[zsel], minlength=n)[keep]
+    # renumber by descending adjacency count of the quotient (stable)
+    order = np.argsort(-cnt, kind='stable')
+    old = keep[order]                                   # new -> packed id of the full graph
+    nq = len(old)
+    rank = np.full(n, -1, dtype=np.int64)
+    rank[old] = np.arange(nq)
+    qi, qj = rank[zi[zsel]], rank[zj[zsel]]
+    zorder = np.lexsort((qj, qi))
+    qi, qj, zsel = qi[zorder], qj[zorder], zsel[zorder]
+    nnz = len(zsel)
+    nz = np.zeros(nnz, dtype=NZ_DTYPE)
+    nz['i'], nz['j'] = qi, qj
+    rowptr = np.concatenate(([0], np.cumsum(cnt[order]))).astype(np.uint16)
+    parts = (np.asarray(dg.degree, dtype=np.float32)[old],
+             np.sqrt(mult[order].astype(np.float64)),
+             np.ascontiguousarray(nodes[old]), rowptr, nz,
+             np.ascontiguousarray(edges[zsel]),
+             np.asarray(dg.perm, dtype=np.uint16)[old])
+    offs, cursor = [], 0
+    for arr in parts:
+        offs.append(cursor)
+        cursor += _pad(arr.nbytes)
+    blob = np.zeros(max(cursor, _ALIGN), dtype=np.uint8)
+    for off, arr in zip(offs, parts):
+        if arr.nbytes:
+            blob[off:off + arr.nbytes] = arr.view(np.uint8).ravel()
+    return blob, offs, nq, nnz
+
+
+def quotient_graph(dg, native=True):
+    """The twin-leaf quotient image of the packed graph `dg` (DESIGN.md
+    section 4a): an ordinary image of the graph with every twin group
+    (`twin_groups`) merged into its representative -- nodes renumbered by
+    descending adjacency count of the QUOTIENT, `degree` the degrees of the
+    FULL graph, `perm` the caller's ids of the representatives -- plus a
+    section `scale` of float64 sqrt(multiplicity) per node between the degrees
+    and the node records, and `n_orig`, the node count of the full graph (the
+    high half of the header's n_node).  The solver multiplies the
+    off-diagonal entries by scale(i) scale(j) (mgk_oc.h QUOT).  None for
+    graphs with variable-length attributes."""
+    if len(dg.relocs):
+        return None
+    if native:
+        from ...hip import hostlib
+        blob, offs, nq, nnz = hostlib.quotient_graph(dg)
+    else:
+        blob, offs, nq, nnz = _quotient_blob_numpy(dg)
+    q = DeviceGraph.__new__(DeviceGraph)
+    q.n_node, q.n_nz, q.n_orig, q.weighted = nq, nnz, dg.n_node, dg.weighted
+    q.node_t, q.edge_t, q.signature = dg.node_t, dg.edge_t, dg.signature
+    q.offsets = dict(zip(QUOTIENT_SECTIONS, offs))
+    o = q.offsets
+    q.blob = blob
+    q.degree = blob[o['degree']:o['degree'] + 4 * nq].view(np.float32)
+    q.scale = blob[o['scale']:o['scale'] + 8 * nq].view(np.float64)
+    q.rowptr = blob[o['rowptr']:o['rowptr'] + 2 * (nq + 1)].view(np.uint16)
+    q.nz = blob[o['nz']:o['nz'] + 4 * nnz].view(NZ_DTYPE)
+    q.perm = blob[o['perm']:o['perm'] + 2 * nq].view(np.uint16)
+    q.adjacency_count = np.diff(q.rowptr.astype(np.int64))
+    q.image_bytes = _pad(o['perm'] + 2 * nq)
+    q.relocs = np.zeros(0, dtype=np.int64)
+    q.n_merged = dg.n_node - nq
+    return q
+
+
 def class_bytes(n_node, n_nz):
     """Bytes of the label-class section that precedes a graph's blob in the
     arena: u8 node classes [pad4(n_node)] then u8 edge classes [pad4(n_nz)],
@@ -969,6 +1092,12 @@ class GraphArena:
         if self.n:
             n_node, n_nz = feat['n_node'], feat['n_nz']
             hdr['n_node'], hdr['n_nz'] = n_node, n_nz
+            if getattr(dgraphs[0], 'n_orig', None) is not None:
+                # quotient images: the node count of the full graph in the
+                # high half of n_node (graph.h)
+                hdr['n_node'] = (n_node | (np.array(
+                    [g.n_orig for g in dgraphs], dtype=np.int64) << 16)
+                ).astype(np.uint32).view(np.int32)
             for s_, name in enumerate(SECTIONS):   # arena-relative for now
                 hdr[name] = starts + (
                     b0['sec_off'][:, s_] if b0 is not None else np.array(
@@ -988,7 +1117,7 @@ class GraphArena:
         self._hdr = hdr
         self._relocs = (np.concatenate(self._relocs) if self._relocs
                         else np.zeros(0, np.int64))
-        self.n_node = hdr['n_node'].astype(np.int64)
+        self.n_node = hdr['n_node'].astype(np.int64) & 0xFFFF
         self.n_nz = hdr['n_nz'].astype(np.int64)
 
     def relocated(self, base):

@@ -190,7 +190,7 @@ class ShardPlan:
     def __init__(self, ji, jj, n_node, n_nz, nX, nY, symmetric, rank,
                  world_size, launch_order=None, times=None, group=None,
                  tail=0.0, snap=2048, mode=None, group_tail=None,
-                 merge_map=None):
+                 merge_map=None, quotient=None):
         """`launch_order`, `times`, `group` (optional): the job ids in the
         backend's launch order (by solver variant, then descending cost), the
         predicted time of every job (`job_times`) and its solver variant --
@@ -204,6 +204,10 @@ class ShardPlan:
         #: variant index it rides in}): every rank applies it to its shard,
         #: so which solver a pair runs on does not depend on the rank count
         self.merge_map = merge_map
+        #: the launch merging of the call on its twin-leaf quotient images
+        #:, decided on the whole job list like `merge_map`, or
+        #: None: the call keeps the full images
+        self.quotient = quotient
         cost = predict_cost(np.asarray(n_node), np.asarray(n_nz),
                             self.ji, self.jj)
         self.mode = 'snake'
@@ -260,7 +264,7 @@ class ShardPlan:
                          launch_order=md['launch_order'], times=times,
                          group=md['group'], tail=md['tail'], snap=md['snap'],
                          group_tail=md['group_tail'],
-                         merge_map=self.merge_map)
+                         merge_map=self.merge_map, quotient=self.quotient)
 
     def scatter_index(self, starts_x, starts_y):
         """Flat F-order destinations (and mirrored destinations) of the
@@ -346,6 +350,21 @@ def measured_shard_plan(backend, graphs, node_kernel, edge_kernel, jobs, nX,
     part = backend._partition(dgraphs, jobs, C, tab_bytes, gtab,
                               nodal=traits.nodal is not False,
                               mfma=backend._label_blind(edge_kernel_in))
+    # Plain value calls run on the twin-leaf quotient images where a plain
+    # HIPBackend takes them for the WHOLE list: decided here, with
+    # the launch merging of the quotient list, and applied by every rank.
+    # (The cuts and the predicted times stay those of the full images: the
+    # cost table knows their variants, and the ranks re-balance by
+    # measurement.)
+    quotient = None
+    qgraphs = backend._quotient_graphs(graphs, dgraphs, traits, C)
+    if qgraphs is not None:
+        qarena = backend._host_arena(qgraphs, fields)
+        qpart = backend._partition(
+            qgraphs, jobs, C, backend._table_bytes(qarena),
+            backend._global_tables(qarena), nodal=False, mfma=False)
+        if backend._quotient_launches(qpart[3]):
+            quotient = dict(qpart.merge_map)
     _, used, order_all, launches = part
     merge_map = dict(part.merge_map)
     ji, jj = jobs['i'].astype(np.int64), jobs['j'].astype(np.int64)
@@ -369,7 +388,7 @@ def measured_shard_plan(backend, graphs, node_kernel, edge_kernel, jobs, nX,
                      bool(traits.symmetric), rank, world,
                      launch_order=order_all.astype(np.int64), times=times,
                      group=group, tail=tail, group_tail=group_tail,
-                     merge_map=merge_map)
+                     merge_map=merge_map, quotient=quotient)
 
 
 def balance_by_measurement(step, plan, build, rounds=2, group=None):
@@ -548,7 +567,8 @@ class ShardedStep:
             self.local_jobs, starts, nX, nY, nJ, traits, timer, packed=True,
             gramian_ptr=out.data_ptr(),
             gradient_ptr=out.data_ptr() + self.capacity * rs.itemsize,
-            merge_map=self.shard.merge_map)
+            merge_map=self.shard.merge_map,
+            quotient=getattr(self.shard, 'quotient', None))
             for out in self.local_outs]
         self.plan = self.plans[0]
 
