@@ -5,8 +5,8 @@
 // There are two wave sums in this tree and they are NOT interchangeable: they
 // add the 64 lanes in different orders and so differ in the last bits.
 //   wave_sum (here): the __shfl_xor butterfly; every lane gets the total.
-//     Used by lowrank.hip, field.hip, outlier.hip, select.hip, laplace.hip
-//     and subspace.hip.
+//     Used by lowrank.hip, field.hip, outlier.hip, select.hip, laplace.hip,
+//     subspace.hip and lloyd.hip.
 //   graphdot::wave::sum (wave.h): DPP row sums chained into lane 63.  Used by
 //     posterior.hip and the solvers.
 // A kernel that moved from one to the other would change its results.

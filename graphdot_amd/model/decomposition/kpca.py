@@ -24,7 +24,7 @@ torch (`_subspace.*_torch`)."""
 import time
 import warnings
 import numpy as np
-from .._device_kernel import device_call, on_device
+from .._matrices import KernelMatrices
 from . import _subspace
 
 SOLVERS = ('auto', 'dense', 'subspace')
@@ -35,7 +35,7 @@ def _torch():
     return torch
 
 
-class KernelPCA:
+class KernelPCA(KernelMatrices):
     """The k leading principal components of graphs under a kernel.
 
     Parameters
@@ -83,69 +83,6 @@ class KernelPCA:
         self.kernel_options = dict(kernel_options or {})
         self.device = device
         self.random_state = random_state
-
-    # -- the matrices ----------------------------------------------------------------
-    def _dense(self):
-        from ..gaussian_process.gpr import _Dense
-        if getattr(self, '_la_device', None) != self.device \
-                or not hasattr(self, '_la'):
-            self._la, self._la_device = _Dense(self.device), self.device
-        return self._la
-
-    @property
-    def _precomputed(self):
-        return isinstance(self.kernel, str) and self.kernel == 'precomputed'
-
-    def _given(self, M, shape, device=None):
-        """A matrix handed in as it lies: a tensor stays on its device (or
-        goes to `device`), an array goes to the algebra's."""
-        torch = _torch()
-        if torch.is_tensor(M):
-            M = M.detach()
-            if device is not None and M.device != device:
-                M = M.to(device)
-        else:
-            M = np.asarray(M)
-            if M.dtype not in (np.float32, np.float64):
-                M = M.astype(np.float64)
-            M = torch.from_numpy(np.ascontiguousarray(M)).to(
-                device if device is not None else self._dense().device)
-        if M.dtype not in (torch.float32, torch.float64):
-            M = M.to(torch.float64)
-        if M.dim() != 2 or any(s is not None and s != t
-                               for s, t in zip(shape, M.shape)):
-            raise ValueError(f'a matrix of shape {shape} expected, got '
-                             f'{tuple(M.shape)}')
-        return M
-
-    def _gram(self, X):
-        """(K as a tensor where the algebra runs, from the device path?)"""
-        if self._precomputed:
-            K = self._given(X, (None, None))
-            if K.shape[0] != K.shape[1]:
-                raise ValueError('precomputed: a square matrix expected, got '
-                                 f'{tuple(K.shape)}')
-            return K, False
-        la = self._dense()
-        if on_device(la, self.kernel_options):
-            Kd = device_call(self.kernel, 'device_gram', X)
-            if Kd is not None:
-                # adopted where the solver wrote it, in its arithmetic and
-                # layout; valid until the next evaluation on that backend
-                return _torch().as_tensor(Kd, device=la.device), True
-        return la.tensor(self.kernel(X, **self.kernel_options)), False
-
-    def _cross(self, Z, device):
-        if self._precomputed:
-            return self._given(Z, (None, self._n), device)
-        la = self._dense()
-        if on_device(la, self.kernel_options) and device.type == 'cuda':
-            Ks = device_call(self.kernel, 'device_cross_gram', Z, self.X)
-            if Ks is not None:
-                return _torch().as_tensor(Ks, device=device)
-        Ks = np.asarray(self.kernel(Z, self.X, **self.kernel_options),
-                        dtype=np.float64)
-        return _torch().from_numpy(np.ascontiguousarray(Ks)).to(device)
 
     # -- the eigenpairs --------------------------------------------------------------
     @staticmethod
