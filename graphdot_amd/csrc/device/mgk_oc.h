@@ -452,20 +452,49 @@ struct oc_solver {
                                  !NGRAD && !MAXIMIN && !FLY && R == 6;
     constexpr static bool HAS_Y = (!STATIC && !FLY) || LEAN || SEQ || DLDS;   // the [Y] region exists (SEQ: the first system's solution waits there)
     constexpr static int Y_REALS = DLDS ? 2 * R * 64 * W : R * 64 * W * C;    // its size
-    // GRID (static layouts whose first batch has DMAX^2 slots): slot
-    // s = u DMAX + v of the first batch is the term (u-th nonzero of row i1,
-    // v-th nonzero of row i2) of the batch's row, valid if u < d1 and v < d2 --
-    // every row has degrees <= DMAX, so every row of the batch fits the grid.
+    // GRID (static layouts whose first batch has GU x GV slots): slot
+    // s = u GV + v of the first batch is the term (u-th nonzero of row i1,
+    // v-th nonzero of row i2) of the batch's row, valid if u < d1 and v < d2.
     // The labels, columns and table offsets are read once per u and per v
-    // (2 DMAX reads) instead of once per slot (DMAX^2), and a slot is an add
+    // (GU + GV reads) instead of once per slot (GU GV), and a slot is an add
     // for its gather address, an add for its table offset and a select: the
     // running-index walk costs 20 VALU per slot, and the setup is a third of
     // a pair's instructions.
+    // The grid is deduced from the first segment: DMAX^2 -> DMAX x DMAX (every
+    // row has degrees <= DMAX: always valid), DMAX (DMAX - 1) -> DMAX x
+    // (DMAX - 1), (DMAX - 1)^2 -> (DMAX - 1) x (DMAX - 1); any other first
+    // segment keeps the running walk.  A GU x GV grid holds the pairs whose
+    // graphs have largest degrees <= GU and <= GV: the host assigns no other
+    // pair to such a layout (HIPBackend.grid_of), and a grid that is not
+    // square takes the graph of the larger degree in the first role (ORIENT).
+    // Only the graph-level value of quotient images is indifferent to the
+    // roles (the nodal, maximin and second-solution epilogues address their
+    // outputs by the job's own graphs): every other kernel gives a first
+    // segment of DMAX (DMAX - 1) the running walk.
+    constexpr static bool ROLES_FREE = QUOT && !NODAL && !MAXIMIN && !NGRAD && C == 1;
+    template<class L> constexpr static int grid_rows() {
+        if constexpr (L::is_static && !NGRAD && DMAX > 1) {
+            if (L::T.end[0] == DMAX * DMAX) return DMAX;
+            if (L::T.end[0] == DMAX * (DMAX - 1)) return ROLES_FREE ? DMAX : 0;
+            if (L::T.end[0] == (DMAX - 1) * (DMAX - 1)) return DMAX - 1;
+        }
+        return 0;
+    }
     template<class L> constexpr static int grid_slots() {
-        if constexpr (L::is_static && !NGRAD) return L::T.end[0] == DMAX * DMAX ? DMAX * DMAX : 0;
+        if constexpr (L::is_static) return grid_rows<L>() ? L::T.end[0] : 0;
         else return 0;
     }
     constexpr static int G0 = grid_slots<LAY>();
+    constexpr static int GU = G0 ? grid_rows<LAY>() : 1;    // half-terms of graph 1
+    constexpr static int GV = G0 ? G0 / GU : 1;             // ... of graph 2
+    // ORIENT (grids that are not square): the graph with a node of more than
+    // GV neighbours plays graph 1, whichever of the job's two it is -- decided
+    // per job from the degree histograms in the headers (wave-uniform, before
+    // staging).  The kernel value is symmetric in its graphs and the pair's
+    // output cell is addressed by the job's own (i, j): only the order of the
+    // summation changes.
+    constexpr static bool ORIENT = GU != GV;
+    static_assert(!ORIENT || ROLES_FREE, "swapped roles: graph-level values of quotient images only");
     static_assert(G0 == 0 || ONE_PASS, "the grid walk belongs to the one-pass slot setup");
     template<class L> constexpr static bool layout_matches() {
         if constexpr (L::is_static) return L::S == S && L::R == R;
@@ -561,13 +590,12 @@ struct oc_solver {
     struct row_t {        // the row a lane is filling slots for
         int i1, i2, rs1, rs2, d1, d2, prod;
     };
-    constexpr static int GD_ = G0 ? DMAX : 1;
-    constexpr static int GQ_ = QUOT ? GD_ : 1;
-    struct grid_t {       // GRID: the first batch's row as 2 DMAX half-terms
-        unsigned a[GD_], b[GD_];      // element indices (clamped into the row)
-        unsigned j1[GD_], j2[GD_];    // lp byte address = j1[u] + j2[v]
-        unsigned t1[GD_], t2[GD_];    // edge table index = t1[u] + t2[v]
-        bool u[GD_], v[GD_];          // u < d1, v < d2
+    constexpr static int GQU = QUOT ? GU : 1, GQV = QUOT ? GV : 1;
+    struct grid_t {       // GRID: the first batch's row as GU + GV half-terms
+        unsigned a[GU], b[GV];        // element indices (clamped into the row)
+        unsigned j1[GU], j2[GV];      // lp byte address = j1[u] + j2[v]
+        unsigned t1[GU], t2[GV];      // edge table index = t1[u] + t2[v]
+        bool u[GU], v[GV];            // u < d1, v < d2
         int row;                      // i1 * ldp + i2
     };
 
@@ -606,7 +634,23 @@ struct oc_solver {
         for (unsigned t = blockIdx.x; t < prm.n_launch_jobs; t += gridDim.x) {
             const job_t job = scalar_load(prm.jobs + t);
             [[maybe_unused]] int no1 = 0, no2 = 0;     // QUOT: nodes of the full graphs
-            const graph_header_t h1 = load_header(headers + job.i, no1), h2 = load_header(headers + job.j, no2);
+            graph_header_t h1 = load_header(headers + job.i, no1), h2 = load_header(headers + job.j, no2);
+            if constexpr (ORIENT) {
+                // the job's second graph plays graph 1 if it has a node of more
+                // than GV neighbours (wave-uniform: the headers are scalars,
+                // and both are loaded either way)
+                bool flip = false;
+#pragma unroll
+                for (int d = GV + 1; d <= DMAX; ++d) flip |= h2.hist[d] != 0;
+                if (flip) {
+                    const graph_header_t h = h1;
+                    h1 = h2;
+                    h2 = h;
+                    const int no = no1;
+                    no1 = no2;
+                    no2 = no;
+                }
+            }
             const int n1 = h1.n_node, n2 = h2.n_node, N = n1 * n2;
             const int ldp = n2 | 1;            // odd row stride of p: banks spread
             const real q = prm.q, q0 = prm.q0;
@@ -839,26 +883,27 @@ struct oc_solver {
                 return w;
             };
 
-            // GRID: the first batch's row as 2 DMAX half-terms
+            // GRID: the first batch's row as GU + GV half-terms
             auto open_grid = [&](unsigned base, unsigned elem) -> grid_t {
                 const row_t r = open_row(0);
                 const bool live = r.prod > 0;
                 grid_t g;
                 g.row = r.i1 * ldp + r.i2;
+                // (half-terms beyond the degree read element 0 of the row,
+                // dead rows element 0 of the graph)
+                // (graph 2's half-terms: GV <= GU of them)
 #pragma unroll
-                for (int k = 0; k < GD_; ++k) {
+                for (int k = 0; k < GU; ++k) {
                     g.u[k] = k < r.d1;
-                    g.v[k] = k < r.d2;
-                    // (half-terms beyond the degree read element 0 of the row,
-                    // dead rows element 0 of the graph)
+                    if (k < GV) g.v[k] = k < r.d2;
                     g.a[k] = live ? (unsigned)r.rs1 + (g.u[k] ? (unsigned)k : 0u) : 0u;
-                    g.b[k] = live ? (unsigned)r.rs2 + (g.v[k] ? (unsigned)k : 0u) : 0u;
-                    const nz_t z1 = at32(g1.nz, g.a[k]), z2 = at32(g2.nz, g.b[k]);
+                    if (k < GV) g.b[k] = live ? (unsigned)r.rs2 + (g.v[k] ? (unsigned)k : 0u) : 0u;
+                    const nz_t z1 = at32(g1.nz, g.a[k]), z2 = at32(g2.nz, k < GV ? g.b[k] : 0u);
                     g.j1[k] = base + __umul24((unsigned)z1.j, (unsigned)ldp) * elem;
-                    g.j2[k] = (unsigned)z2.j * elem;
+                    if (k < GV) g.j2[k] = (unsigned)z2.j * elem;
                     if constexpr (TAB) {
                         g.t1[k] = __umul24((unsigned)ecls1[g.a[k]], nec);
-                        g.t2[k] = (unsigned)ecls2[g.b[k]];
+                        if (k < GV) g.t2[k] = (unsigned)ecls2[g.b[k]];
                     }
                 }
                 return g;
@@ -908,22 +953,22 @@ struct oc_solver {
                     int kb = 0;
                     walk_t cur = G0 ? walk_t{} : open_walk(0);
                     [[maybe_unused]] grid_t grid;
-                    [[maybe_unused]] edge_t ge1[GD_], ge2[GD_];
-                    [[maybe_unused]] real gw1[GQ_], gw2[GQ_];     // QUOT: s(i) s(j) of the half-terms
+                    [[maybe_unused]] edge_t ge1[GU], ge2[GV];
+                    [[maybe_unused]] real gw1[GQU], gw2[GQV];     // QUOT: s(i) s(j) of the half-terms
                     if constexpr (G0 > 0) {
                         grid = open_grid(lp_off, ELEM);
                         if constexpr (QUOT) {
 #pragma unroll
-                            for (int k = 0; k < GD_; ++k) {
+                            for (int k = 0; k < GU; ++k) {
                                 gw1[k] = qweight(g1, at32(g1.nz, grid.a[k]));
-                                gw2[k] = qweight(g2, at32(g2.nz, grid.b[k]));
+                                if (k < GV) gw2[k] = qweight(g2, at32(g2.nz, grid.b[k]));
                             }
                         }
                         if constexpr (!TAB || (GD_WEIGHTED && edge_weight<edge_t>::value)) {
 #pragma unroll
-                            for (int k = 0; k < GD_; ++k) {
+                            for (int k = 0; k < GU; ++k) {
                                 ge1[k] = at32(g1.edge, grid.a[k]);
-                                ge2[k] = at32(g2.edge, grid.b[k]);
+                                if (k < GV) ge2[k] = at32(g2.edge, grid.b[k]);
                             }
                         }
                     }
@@ -936,7 +981,7 @@ struct oc_solver {
                         bool ok;
                         unsigned col;
                         if (s < G0) {
-                            const int gu = s / GD_, gv = s % GD_;
+                            const int gu = s / GV, gv = s % GV;
                             ok = grid.u[gu] && grid.v[gv];
                             if constexpr (TAB) {
                                 e = at32(ketab, grid.t1[gu] + grid.t2[gv]);
@@ -2280,9 +2325,9 @@ struct oc_solver {
 #pragma unroll
                     for (int s = 0; s < S; ++s) {
                         if (s < n_slots) {   // wave-uniform
-                            const bool ok = s < G0 ? grid.u[s / GD_] && grid.v[s % GD_] : cur.valid();
-                            const unsigned a = s < G0 ? grid.a[s / GD_] : cur.a();
-                            const unsigned b = s < G0 ? grid.b[s % GD_] : cur.e2;
+                            const bool ok = s < G0 ? grid.u[s / GV] && grid.v[s % GV] : cur.valid();
+                            const unsigned a = s < G0 ? grid.a[s / GV] : cur.a();
+                            const unsigned b = s < G0 ? grid.b[s % GV] : cur.e2;
                             real w = ok ? yrow * load_real_at<real>(adr[s]) : real(0);
                             if constexpr (TAB) {
                                 const unsigned cidx = __umul24((unsigned)ecls1[a], nec) + ecls2[b];

@@ -525,9 +525,22 @@ int gdh_classify_oc(int64_t n_pairs, const int32_t *ca, const int32_t *cb,
             const bool fly = S[v] == 0;
             if (!fly && (pmd_true > D[v] || pmd_true > 14)) continue;
             const int64_t T = 64 * (int64_t)W[v];
-            if (N > T * R[v] || np_ >= (fly ? 0x3FFF : 0xFFFF)) continue;
+            // the grid of the first batch of a static layout (mgk_oc.h GRID,
+            // HIPBackend.grid_of): gu x gv half-terms, 0: the running walk
+            int gu = 0, gv = 0;
+            if (n_L[v] > 0 && D[v] > 1) {
+                const int l0 = L[(size_t)v * MAXL], d = D[v];
+                if (l0 == d * d) gu = gv = d;
+                else if (l0 == d * (d - 1)) gu = d, gv = d - 1;
+                else if (l0 == (d - 1) * (d - 1)) gu = gv = d - 1;
+            }
+            // a grid that is not square takes either graph in the first role
+            // (mgk_oc.h ORIENT): p is sized for the larger of the two orders
+            const int64_t np_v = gu != gv ? std::max(np_, n2 * (n1 | 1)) : np_;
+            if (N > T * R[v] || np_v >= (fly ? 0x3FFF : 0xFFFF)) continue;
+            if (gu && (pmd_true > gu || std::min(maxdeg[a], maxdeg[b]) > gv)) continue;
             const int64_t NR = T * R[v];
-            const int64_t pcap = (np_ + 1 + 3) / 4 * 4;
+            const int64_t pcap = (np_v + 1 + 3) / 4 * 4;
             const int64_t NRy = ((n_L[v] > 0 && C != 2) || fly) ? 0 : NR;
             const int64_t lds = (pcap + NRy) * C * real_size + 4 * NR + 2 * gbytes +
                                 4 * (int64_t)W[v] * real_size + 4 * (D[v] > 6 ? 128 : 64) + 256 + 16 +

@@ -110,8 +110,16 @@ VARIANTS = [
 #: (degrees <= 4: the first batch holds the 16-term rows of two four-valent
 #: atoms, then 4 = 2 x 2 / 4 x 1, then hydrogens): on the QM7-like set 66
 #: distinct profiles, all under one of these.
+#: The twin-leaf quotient images have lost most of their
+#: leaves: the first rows of a quotient pair have 16, 12 or 9 terms (largest
+#: degrees 4 x 4, 4 x 3, 3 x 3) and no second batch opens with more than 3 on
+#: all but 3 % of the QM7-like pairs.  OC_QUOTIENT_LAYOUTS are cut to that; they
+#: are offered to the plans on quotient images only (C = 1, graph-level values)
+#: -- every other path keeps the menu its occupancy targets were swept with.
+OC_QUOTIENT_LAYOUTS = ((12, 3), (16, 3), (12, 3, 1), (16, 3, 1))
 OC_STATIC_VARIANTS = [
-    OCStatic(16), OCStatic(16, 4), OCStatic(16, 4, 1), OCStatic(16, 4, 4),
+    OCStatic(12, 3), OCStatic(16), OCStatic(16, 3), OCStatic(16, 4),
+    OCStatic(12, 3, 1), OCStatic(16, 3, 1), OCStatic(16, 4, 1), OCStatic(16, 4, 4),
     OCStatic(16, 4, 4, 1), OCStatic(16, 4, 4, 1, 1), OCStatic(16, 4, 4, 3, 1),
     OCStatic(16, 4, 4, 3, 1, 1), OCStatic(16, 4, 4, 4, 1, 1, 1),
     OCStatic(16, 4, 4, 4, 3, 1, 1, 1), OCStatic(16, 4, 4, 4, 4, 1, 1, 1, 1),
@@ -947,6 +955,9 @@ struct ${name}_t : ${name}_theta_t {
     #: scratch per pair to HBM, profiles/r02_f32_pmc.csv: not taken)
     _OC_WAVES = {
         (False, 1): {('L', 16): 6, ('L', 16, 4): 6, ('L', 16, 4, 1): 5, ('L', 16, 4, 4): 5,
+                     # (the layouts of quotient images, OC_QUOTIENT_LAYOUTS:
+                     # the targets of (16,4) and (16,4,1), not yet swept)
+                     ('L', 12, 3): 6, ('L', 16, 3): 6, ('L', 12, 3, 1): 5, ('L', 16, 3, 1): 5,
                      ('L', 16, 4, 4, 1): 3, ('L', 16, 4, 4, 1, 1): 3,
                      ('L', 16, 4, 4, 3, 1): 4, ('L', 16, 4, 4, 3, 1, 1): 4,
                      ('L', 16, 4, 4, 4, 1, 1, 1): 3,
@@ -961,6 +972,10 @@ struct ${name}_t : ${name}_theta_t {
                      (8, 64, 4, 8): 4, (16, 32, 2, 8): 4, (16, 40, 2, 8): 4,
                      (16, 48, 3, 8): 4, (16, 64, 3, 8): 4},
         (True, 1): {('L', 16): 4, ('L', 16, 4): 4, ('L', 16, 4, 1): 3, ('L', 16, 4, 4): 3,
+                    # (OC_QUOTIENT_LAYOUTS: the targets of (16,4) and (16,4,1),
+                    # not yet swept; (12,3) is spill-free at four waves with
+                    # 122 registers, the three-batch ones at three)
+                    ('L', 12, 3): 4, ('L', 16, 3): 4, ('L', 12, 3, 1): 3, ('L', 16, 3, 1): 3,
                     # (round 5: the five-batch layouts at three waves -- with
                     # the row sums zeroed late and p updated in place
                     # (mgk_oc.h) their iteration is spill-free at 168
@@ -1019,9 +1034,53 @@ struct ${name}_t : ${name}_theta_t {
     #: (mgk_oc.h SEQ) and are back in the menu.
     _STATIC_OFF = {}
 
-    def _static_enabled(self, v, C):
+    def _static_enabled(self, v, C, quot=True):
+        """Is the static layout of `v` on the menu of a plan with C right-hand
+        sides, on quotient images (`quot`) or full ones?"""
         f64 = np.dtype(self.real) == np.float64
+        if v.L in OC_QUOTIENT_LAYOUTS and not quot:
+            return False
         return v.L not in self._STATIC_OFF.get((f64, C), ())
+
+    @staticmethod
+    def grid_of(L, D):
+        """(GU, GV) of the grid walk that mgk_oc.h gives the first batch of the
+        static layout L of a D-kernel (oc_solver::grid_rows), or None: the
+        running walk.  A pair fits the grid if the larger of its graphs'
+        largest degrees is <= GU and the smaller <= GV.  (A grid that is not
+        square exists in the graph-level value kernels of quotient images
+        only, the plans OC_QUOTIENT_LAYOUTS are offered to; there the kernel
+        takes either graph in the first role, and the host sizes p for
+        both.)"""
+        if not L or D < 2:
+            return None
+        if L[0] in (D * D, D * (D - 1)):
+            return D, L[0] // D
+        if L[0] == (D - 1) * (D - 1):
+            return D - 1, D - 1
+        return None
+
+    @classmethod
+    def swaps_roles(cls, v, maxdeg_j):
+        """Does the kernel of variant `v` give the second graph of a job the
+        first role (mgk_oc.h ORIENT)?  In a grid that is not square, when that
+        graph -- of largest degree `maxdeg_j`, an array -- has a node of more
+        than GV neighbours."""
+        g = cls.grid_of(v.L, v.D) if isinstance(v, OCVariant) else None
+        maxdeg_j = np.asarray(maxdeg_j)
+        if g is None or g[0] == g[1]:
+            return np.zeros(maxdeg_j.shape, dtype=bool)
+        return maxdeg_j > g[1]
+
+    @classmethod
+    def _grid_takes(cls, v2, v):
+        """May the pairs of the static layout `v` ride in the static layout
+        `v2` -- does every pair that fits v's first batch fit v2's grid?"""
+        g2 = cls.grid_of(v2.L, v2.D)
+        if g2 is None or g2 == (v2.D, v2.D):
+            return True
+        g = cls.grid_of(v.L, v.D)
+        return g is not None and g[0] <= g2[0] and g[1] <= g2[1]
 
     _FLY_WAVES = 3     # (occupancy 3-6 waves per SIMD: 4.95-4.86 M pairs/s, round 3)
 
@@ -1489,6 +1548,14 @@ void ${name}(params_t prm) {
         nnz1 = n_nz[ji]
         N = n1 * n2
         NP = n1 * (n2 | 1)                 # row space with the odd LDS stride
+        # ... of a kernel that may take either graph in the first role
+        # (mgk_oc.h ORIENT: grids that are not square): n1 (n2 | 1) is not
+        # symmetric -- 8 x 9 is 72, 9 x 8 is 81 -- so the larger of both orders
+        NP_either = np.maximum(NP, n2 * (n1 | 1))
+
+        def rows_of(v):
+            g = self.grid_of(v.L, v.D) if isinstance(v, OCVariant) else None
+            return NP_either if g is not None and g[0] != g[1] else NP
         cost = n_nz[ji] * n_nz[jj] + 4 * N
         choice = np.full(len(ji), -1, dtype=np.int64)
         slots = {}
@@ -1515,14 +1582,28 @@ void ${name}(params_t prm) {
         # tests of the loop below), when it precedes every other variant
         is_oc = [isinstance(v, OCVariant) for v in self.variants]
         n_oc = sum(is_oc)
+        # the layouts cut for quotient images: plain values on such images
+        quot = bool(C == 1 and not nodal and len(dgraphs) and
+                    getattr(dgraphs[0], 'n_orig', None) is not None)
+
+        def grid_fits(v, idx):
+            """Grid rule: the pairs `idx` whose largest degrees fit the grid
+            of the first batch of v's layout (mgk_oc.h GRID; implied by the
+            cap of the first batch unless the grid is narrower than D)."""
+            g = self.grid_of(v.L, v.D)
+            if g is None:
+                return np.ones(len(idx), dtype=bool)
+            a, b = maxdeg[ji[idx]], maxdeg[jj[idx]]
+            return (np.maximum(a, b) <= g[0]) & (np.minimum(a, b) <= g[1])
+        menu = [(k, v) for k, v in enumerate(self.variants[:n_oc])
+                if isinstance(v, OCVariant)
+                and (not v.L or self._static_enabled(v, C, quot))
+                and (v.S > 0 or not fly_off)]
         native_oc = (self.native and not tab_bytes and n_oc > 0
                      and all(is_oc[:n_oc]) and len(ji) > 0
                      and len(dgraphs) < 2**31)
         if native_oc:
             from ...hip import hostlib
-            menu = [(k, v) for k, v in enumerate(self.variants[:n_oc])
-                    if (not v.L or self._static_enabled(v, C))
-                    and (v.S > 0 or not fly_off)]
             hist = f['hist']
             ch, _ = hostlib.classify_oc(
                 ji, jj, n_node, n_nz, image_oc, maxdeg, hist,
@@ -1542,7 +1623,7 @@ void ${name}(params_t prm) {
             if isinstance(v, OCVariant):
                 if tab_bytes or native_oc:  # (table kernels: two-stage only)
                     continue
-                if v.L and not self._static_enabled(v, C):
+                if v.L and not self._static_enabled(v, C, quot):
                     continue
                 if v.S == 0:
                     # on-the-fly: the pairs whose degrees no slot variant
@@ -1558,11 +1639,12 @@ void ${name}(params_t prm) {
                     choice[rem[fits]] = k
                     rem = rem[~fits]
                     continue
+                NPv = rows_of(v)
                 fits = ((pair_maxdeg[rem] <= v.D) & (N[rem] <= 64 * v.W * v.R)
-                        & (NP[rem] < 0xFFFF))
+                        & (NPv[rem] < 0xFFFF))
                 if not fits.any():
                     continue
-                fits &= self.lds_bytes(v, C, NP[rem], gbytes_oc[rem],
+                fits &= self.lds_bytes(v, C, NPv[rem], gbytes_oc[rem],
                                        nodal=nodal) <= LDS_LIMIT
                 if v.L:
                     # static layout: the trip count of every batch under its
@@ -1576,6 +1658,7 @@ void ${name}(params_t prm) {
                     L = np.zeros(tr.shape[1], dtype=np.int64)
                     L[:v.R] = v.L
                     ok[ok] = (tr[row[idx[ok]]] <= L[None, :]).all(axis=1)
+                    ok &= grid_fits(v, idx)
                     choice[idx[ok]] = k
                     fits[fits] = ok
                     rem = rem[~fits]
@@ -1662,6 +1745,11 @@ void ${name}(params_t prm) {
                 choice[fits] = self.variants.index(STREAM)
                 # (for these pairs `gbytes` is the dynamic LDS of the pair)
                 gbytes = np.where(fits, sb, gbytes)
+        # (the launches size p from this: a pair keeps the larger figure if
+        # its launch is merged into a square grid later)
+        for k in set(choice.tolist()):
+            if k >= 0 and rows_of(self.variants[k]) is NP_either:
+                NP = np.where(choice == k, NP_either, NP)
         return choice, cost, ntask, gbytes, NP, gbytes_oc, np.maximum(n1, n2)
 
     # -- the three phases -----------------------------------------------------------
@@ -1799,19 +1887,21 @@ void ${name}(params_t prm) {
                             and v2.D == v.D and v2.S >= v.S and v2.R >= v.R):
                         continue
                     # a static layout takes the jobs of another static layout
-                    # it dominates batch by batch (never those of a dynamic
-                    # variant); a dynamic variant takes any total <= S
+                    # it dominates batch by batch, first-batch grid included: a
+                    # 12-first launch may ride in a 16-first layout, never the
+                    # reverse (never those of a dynamic variant); a dynamic
+                    # variant takes any total <= S
                     if v2.L and not (v.L and all(
-                            a <= b for a, b in zip(v.L, v2.L))):
+                            a <= b for a, b in zip(v.L, v2.L))
+                            and self._grid_takes(v2, v)):
                         continue
-                    if True:
-                        choice = np.where(here, k2, choice)
-                        # (chains collapse: what rode in k now rides in k2)
-                        for k0, k1 in list(applied.items()):
-                            if k1 == k:
-                                applied[k0] = k2
-                        applied[k] = k2
-                        break
+                    choice = np.where(here, k2, choice)
+                    # (chains collapse: what rode in k now rides in k2)
+                    for k0, k1 in list(applied.items()):
+                        if k1 == k:
+                            applied[k0] = k2
+                    applied[k] = k2
+                    break
         choice = self._fit_launches_into_lds(choice, C, NP, ntask, gbytes,
                                              gbytes_oc, tab_bytes, oc_only,
                                              nodal)

@@ -2,8 +2,9 @@
 """Dump the gfx950 ISA of one solver variant built for the bench workload
 (QM7-like TensorProduct kernels) -- for instruction-count work on the CG loop.
 
-    python scripts/dump_isa.py W S R [C] [--f64] [--oc=D] [--layout=16x4x4x1] [--tab|--tab=2] [--config2|--tang] [--maximin|--m3] > out.s
+    python scripts/dump_isa.py W S R [C] [--f64] [--oc=D] [--layout=16x4x4x1] [--tab|--tab=2] [--quot] [--config2|--tang] [--maximin|--m3] > out.s
 
+--quot: the solver of the twin-leaf quotient images (mgk_oc.h QUOT).
 --maximin / --m3: the fused epilogue flavours of the owner-computes solvers
 (nodal value solve, direct microkernel evaluation; --m3 needs --f64).
 """
@@ -53,7 +54,8 @@ if flavour:
 else:
     src = backend.render_source(kn, ke2, k.p, node_t, edge_t, [variant], C,
                                 tab=2 if '--tab=2' in sys.argv else '--tab' in sys.argv,
-                                weighted=dgs[0].weighted)
+                                weighted=dgs[0].weighted,
+                                quot='--quot' in sys.argv)
 path = f'/tmp/_dump_isa_{W}_{S}_{R}_{C}_{int(real is np.float64)}_{flavour}.hip'
 open(path, 'w').write(src)
 flags = [f for f in jit.BASE_FLAGS if f != '--genco'] + \
