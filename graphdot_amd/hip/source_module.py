@@ -85,6 +85,7 @@ STATIC_SOURCES = (
     'model/gaussian_process/laplace.hip',
     'model/decomposition/subspace.hip',
     'model/clustering/lloyd.hip',
+    'model/svm/smo.hip',
 )
 #: file name -> SourceModule
 STATIC = {os.path.basename(p): SourceModule(os.path.join(_PACKAGE, p))

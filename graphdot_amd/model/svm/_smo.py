@@ -1,0 +1,281 @@
+"""Host side of smo.hip, the SMO solver and the decision sums behind
+`KernelSVC`: compiles the kernels once (JIT cache of graphdot_amd.hip.jit,
+IEEE arithmetic: no fast-math) and runs them on torch's *current* stream of
+the matrix's device, in stream order with the torch operations around them.
+Both launches have a ``*_torch`` restatement on any device: the yardstick of
+the kernels and the host path of the model.
+
+A batch of P problems shares the (n, n) matrix: ``y`` (P, n) int8 in {+1, -1}
+and the upper bounds ``U`` (P, n) float64, ``U = 0`` for a sample that is not
+part of the problem.  Each minimises ``f(alpha) = 1/2 sum alpha_i alpha_j y_i
+y_j K_ij - sum alpha_i`` subject to ``0 <= alpha <= U`` and ``y^T alpha = 0``
+by SMO with the second-order working-set rule of Fan, Chen and Lin (the rule
+libsvm uses), every choice taking the lowest index on a tie, all of it in
+double whatever the type of K.
+
+The fused path keeps ``G`` and ``alpha`` of a problem in LDS: 16 bytes per
+sample of the 64 KB of static LDS, less 512 bytes for what the four waves
+exchange in the two reductions of a step, so ``NMAX = (65536 - 512) / 16 =
+4064``.  Larger matrices, CPU tensors and other devices take `smo_torch`."""
+import numpy as np
+from ...hip.source_module import STATIC, chunk, current_stream, suffix
+from ..decomposition._subspace import _check_K, _f64
+
+_module = STATIC['smo.hip']
+precompile = _module.precompile
+_BLOCK = 256
+_WAVE = 64
+_LDS = 65536        # static LDS of a workgroup
+_EXCHANGE = 512     # of which the reductions' exchange
+NMAX = (_LDS - _EXCHANGE) // 16
+TAU = 1e-12         # the curvature where K_ii + K_jj - 2 K_ij is not positive
+#: steps per launch: the host looks at `info` (4 P numbers) after each
+SLICE = 2048
+
+
+class Result:
+    """`alpha`, `G` (P, n) and `info` (P, 4) = [steps, m, M, status] as
+    tensors where the matrix is; `slices`: the launches (looks of the host)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def stopped(info, tol, max_iter):
+    """(P,) bool from `info` as a numpy array."""
+    with np.errstate(invalid='ignore'):
+        return (info[:, 3] != 0) | (info[:, 1] - info[:, 2] < tol) \
+            | (info[:, 0] >= max_iter)
+
+
+def _check_batch(y, U, n):
+    import torch
+    if not torch.is_tensor(y) or y.dtype != torch.int8 or y.dim() != 2 \
+            or y.shape[1] != n or y.shape[0] < 1:
+        raise TypeError(f'y: (P, {n}) int8 expected')
+    if not torch.is_tensor(U) or U.dtype != torch.float64 \
+            or U.shape != y.shape:
+        raise TypeError(f'U: {tuple(y.shape)} float64 expected')
+    return y.shape[0]
+
+
+def _check_limits(tol, max_iter, steps=1):
+    if not tol > 0:
+        raise ValueError(f'tol: a positive number expected, got {tol}')
+    for name, v in (('max_iter', max_iter), ('steps', steps)):
+        if int(v) != v or v < 1:
+            raise ValueError(f'{name}: a positive integer expected, got {v}')
+
+
+def start(P, n, device):
+    """(state (P, 2, n) = [alpha = 0 | G = -1], info (P, 4) = [0, inf, -inf,
+    0]) of a batch before its first step."""
+    import torch
+    state = torch.zeros((P, 2, n), dtype=torch.float64, device=device)
+    state[:, 1] = -1.0
+    info = torch.zeros((P, 4), dtype=torch.float64, device=device)
+    info[:, 1], info[:, 2] = float('inf'), float('-inf')
+    return state, info
+
+
+def smo_slice(K, y, U, state, info, tol, steps, max_iter):
+    """One launch of `svm_smo_*`: at most `steps` steps of every problem that
+    has not stopped, on `state` and `info` in place."""
+    import torch
+    n = _check_K(K)
+    if n > NMAX:
+        raise ValueError(f'n = {n}: at most NMAX = {NMAX} on the fused path; '
+                         'see smo_torch')
+    dev = K.device
+    P = _check_batch(y, U, n)
+    _check_limits(tol, max_iter, steps)
+    if y.device != dev or U.device != dev:
+        raise ValueError('K, y and U must be on the same device')
+    y, U = y.contiguous(), U.contiguous()
+    state = _f64('state', state, (P, 2, n), dev)
+    info = _f64('info', info, (P, 4), dev)
+    with torch.cuda.device(dev):
+        _module.launch(f'svm_smo_{suffix(K.dtype)}', P, _BLOCK, 'QiQQQQdqq',
+                       K.data_ptr(), n, y.data_ptr(), U.data_ptr(),
+                       state.data_ptr(), info.data_ptr(), float(tol),
+                       int(steps), int(max_iter), stream=current_stream(dev))
+    return state, info
+
+
+def smo(K, y, U, tol=1e-3, max_iter=1_000_000, steps=SLICE):
+    """The batch solved by relaunching `svm_smo_*` until every problem has
+    stopped (``m - M < tol``, `max_iter` steps, or a status): one download of
+    `info` per launch, nothing else.
+
+    K: (n, n) float32 or float64 CUDA tensor, n <= NMAX, symmetric, contiguous
+    along either index, 16-byte aligned (read as it lies)."""
+    n = _check_K(K)
+    P = _check_batch(y, U, n)
+    _check_limits(tol, max_iter, steps)
+    y, U = y.contiguous(), U.contiguous()
+    state, info = start(P, n, K.device)
+    slices = 0
+    while True:
+        smo_slice(K, y, U, state, info, tol, steps, max_iter)
+        slices += 1
+        if stopped(info.cpu().numpy(), tol, max_iter).all():
+            break
+    return Result(alpha=state[:, 0], G=state[:, 1], info=info, slices=slices)
+
+
+def _pair(ai, aj, Gi, Gj, Ui, Uj, differ, q):
+    """libsvm's update of a pair along the constraint, clipped to its box, for
+    every problem at once."""
+    import torch
+    w = torch.where
+    zero = torch.zeros_like(ai)
+    # y_i != y_j
+    delta, diff = (-Gi - Gj) / q, ai - aj
+    ni, nj = ai + delta, aj + delta
+    c = diff > 0
+    t = c & (nj < 0)
+    ni, nj = w(t, diff, ni), w(t, zero, nj)
+    t = ~c & (ni < 0)
+    ni, nj = w(t, zero, ni), w(t, -diff, nj)
+    c = diff > Ui - Uj
+    t = c & (ni > Ui)
+    ni, nj = w(t, Ui, ni), w(t, Ui - diff, nj)
+    t = ~c & (nj > Uj)
+    ni, nj = w(t, Uj + diff, ni), w(t, Uj, nj)
+    # y_i == y_j
+    delta, tot = (Gi - Gj) / q, ai + aj
+    si, sj = ai - delta, aj + delta
+    c = tot > Ui
+    t = c & (si > Ui)
+    si, sj = w(t, Ui, si), w(t, tot - Ui, sj)
+    t = ~c & (sj < 0)
+    si, sj = w(t, tot, si), w(t, zero, sj)
+    c = tot > Uj
+    t = c & (sj > Uj)
+    si, sj = w(t, tot - Uj, si), w(t, Uj, sj)
+    t = ~c & (si < 0)
+    si, sj = w(t, zero, si), w(t, tot, sj)
+    ni, nj = w(differ, ni, si), w(differ, nj, sj)
+    # (the partner is a rounded difference: the clamp keeps it in its box)
+    return torch.minimum(torch.clamp_min(ni, 0.0), Ui), \
+        torch.minimum(torch.clamp_min(nj, 0.0), Uj)
+
+
+def smo_torch(K, y, U, tol=1e-3, max_iter=1_000_000):
+    """The same rule with torch operations, all problems advancing together
+    (one that has stopped is left unchanged); one look per step."""
+    import torch
+    n = K.shape[0]
+    P = _check_batch(y, U, n)
+    _check_limits(tol, max_iter)
+    K = K.to(torch.float64)
+    dev = K.device
+    y, U = y.to(dev), U.to(dev)
+    diag = K.diagonal()
+    yf = y.to(torch.float64)
+    pos = y > 0
+    state, info = start(P, n, dev)
+    alpha, G = state[:, 0], state[:, 1]
+    inf = torch.full((P, n), float('inf'), dtype=torch.float64, device=dev)
+    done = torch.zeros(P, dtype=torch.float64, device=dev)
+    status = torch.zeros(P, dtype=torch.bool, device=dev)
+    if not bool(torch.isfinite(diag).all()):
+        status[:] = True
+    col = torch.arange(P, device=dev)
+    looks = 0
+    while True:
+        v = -yf * G
+        up = torch.where(pos, alpha < U, alpha > 0)
+        low = torch.where(pos, alpha > 0, alpha < U)
+        m, i = torch.where(up, v, -inf).max(1)       # (the first on a tie)
+        M = torch.where(low, v, inf).min(1).values
+        status |= ~torch.isfinite(G).all(1)
+        run = ~status & ~(m - M < tol) & (done < max_iter)
+        looks += 1
+        if not bool(run.any()):
+            break
+        Ki = K.index_select(0, i)
+        b = m[:, None] - v
+        a = (diag[i][:, None] + diag[None, :]) - 2.0 * Ki
+        a = torch.where(a <= 0, torch.full_like(a, TAU), a)
+        cand = low & (v < m[:, None])
+        obj = torch.where(cand, -(b * b) / a, inf)
+        none = ~cand.any(1) | torch.isnan(obj).any(1)
+        j = torch.where(torch.isnan(obj), inf, obj).argmin(1)
+        Kj = K.index_select(0, j)
+        ai, aj = alpha[col, i], alpha[col, j]
+        ni, nj = _pair(ai, aj, G[col, i], G[col, j], U[col, i], U[col, j],
+                       y[col, i] != y[col, j], a[col, j])
+        status |= run & none
+        run &= ~none
+        zero = torch.zeros_like(ai)
+        si = torch.where(run, yf[col, i] * (ni - ai), zero)
+        sj = torch.where(run, yf[col, j] * (nj - aj), zero)
+        alpha[col, i] = torch.where(run, ni, ai)
+        alpha[col, j] = torch.where(run, nj, alpha[col, j])
+        G[:] = torch.where(run[:, None],
+                           G + yf * (Ki * si[:, None] + Kj * sj[:, None]), G)
+        done += run.to(torch.float64)
+    info[:, 0], info[:, 1], info[:, 2] = done, m, M
+    info[:, 3] = status.to(torch.float64)
+    return Result(alpha=alpha, G=G, info=info, slices=looks)
+
+
+def solve(K, y, U, tol, max_iter):
+    """(Result, fused?): `smo` for a CUDA matrix of n <= NMAX, `smo_torch`
+    anywhere else."""
+    n = K.shape[0]
+    if K.is_cuda and n <= NMAX:
+        if n > 1 and K.stride() not in ((n, 1), (1, n)) or K.data_ptr() % 16:
+            K = K.contiguous()
+        return smo(K, y.to(K.device), U.to(K.device), tol, max_iter), True
+    return smo_torch(K, y, U, tol, max_iter), False
+
+
+# -- decision values --------------------------------------------------------------
+def decide(Ks, coef, b):
+    """``out[p, r] = sum_j Ks[r, j] coef[p, j] + b[p]`` (P, nb) float64 of
+    `svm_decide_*`, the n terms split over four waves and added in order.
+
+    Ks: (nb, n) float32 or float64 CUDA tensor, any positive strides (read as
+    it lies).  coef: (P, n), b: (P,) float64."""
+    import torch
+    if not coef.is_cuda:
+        raise TypeError('coef: a CUDA tensor expected; see decide_torch')
+    dev = coef.device
+    if coef.dim() != 2 or coef.shape[0] < 1:
+        raise ValueError('coef: (P, n) expected')
+    P, n = coef.shape
+    coef, b = _f64('coef', coef, (P, n), dev), _f64('b', b, (P,), dev)
+    if Ks.dim() != 2 or Ks.shape[1] != n \
+            or Ks.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'Ks: (nb, {n}) float32 or float64 expected')
+    if Ks.device != dev:
+        raise ValueError('Ks and coef must be on the same device')
+    if min(Ks.stride()) < 0:
+        raise ValueError('Ks: negative strides')
+    nb = Ks.shape[0]
+    kc = chunk(P)
+    with torch.cuda.device(dev):
+        out = torch.empty((P, nb), dtype=torch.float64, device=dev)
+        if nb:
+            _module.launch(
+                f'svm_decide_{suffix(Ks.dtype)}_k{kc}',
+                -(-nb // _WAVE) * -(-P // kc), _BLOCK, 'QqqqqQQiQ',
+                Ks.data_ptr(), nb, n, Ks.stride(0), Ks.stride(1),
+                coef.data_ptr(), b.data_ptr(), P, out.data_ptr(),
+                stream=current_stream(dev))
+    return out
+
+
+def decide_torch(Ks, coef, b):
+    """The same, the n terms added one after the other in index order: a
+    sample whose coefficient is zero adds an exact zero, so the values on a
+    matrix and on its sub-matrix without such samples are the same bits."""
+    import torch
+    Ks = Ks.to(torch.float64)
+    P, n = coef.shape
+    out = torch.zeros((P, Ks.shape[0]), dtype=torch.float64, device=Ks.device)
+    for j in range(n):
+        out += coef[:, j, None] * Ks[None, :, j]
+    return out + b[:, None]
