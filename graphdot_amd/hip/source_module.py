@@ -86,6 +86,7 @@ STATIC_SOURCES = (
     'model/decomposition/subspace.hip',
     'model/clustering/lloyd.hip',
     'model/svm/smo.hip',
+    'model/svm/svr.hip',
 )
 #: file name -> SourceModule
 STATIC = {os.path.basename(p): SourceModule(os.path.join(_PACKAGE, p))

@@ -16,7 +16,12 @@ double whatever the type of K.
 The fused path keeps ``G`` and ``alpha`` of a problem in LDS: 16 bytes per
 sample of the 64 KB of static LDS, less 512 bytes for what the four waves
 exchange in the two reductions of a step, so ``NMAX = (65536 - 512) / 16 =
-4064``.  Larger matrices, CPU tensors and other devices take `smo_torch`."""
+4064``.  Larger matrices, CPU tensors and other devices take `smo_torch`.
+
+Below the decision sums: the same solver entered with a given start (`smo_from`,
+`one_class_start`: the one-class problem needs nothing else), and epsilon-SVR
+on svr.hip (`smo2`, `smo2_torch`), whose 2n variables
+over the n samples take 32 bytes of LDS per sample: ``NMAX2 = NMAX // 2``."""
 import numpy as np
 from ...hip.source_module import STATIC, chunk, current_stream, suffix
 from ..decomposition._subspace import _check_K, _f64
@@ -279,3 +284,270 @@ def decide_torch(Ks, coef, b):
     for j in range(n):
         out += coef[:, j, None] * Ks[None, :, j]
     return out + b[:, None]
+
+
+# -- a given start: the one-class problem -------------------------------------------
+def _check_state(state, info, P, n, dev):
+    return _f64('state', state, (P, 2, n), dev), _f64('info', info, (P, 4), dev)
+
+
+def _info0(P, device):
+    """info (P, 4) = [0, inf, -inf, 0] of a batch before its first step."""
+    return start(P, 0, device)[1]
+
+
+def smo_from(K, y, U, state, info, tol=1e-3, max_iter=1_000_000, steps=SLICE):
+    """`smo` entered with a given `state` (P, 2, n) = [alpha | G] and `info`
+    (both advanced in place): any linear term and any feasible start, for `G =
+    Q alpha + p` is all the kernel knows of them."""
+    n = _check_K(K)
+    P = _check_batch(y, U, n)
+    _check_limits(tol, max_iter, steps)
+    y, U = y.contiguous(), U.contiguous()
+    state, info = _check_state(state, info, P, n, K.device)
+    slices = 0
+    while True:
+        smo_slice(K, y, U, state, info, tol, steps, max_iter)
+        slices += 1
+        if stopped(info.cpu().numpy(), tol, max_iter).all():
+            break
+    return Result(alpha=state[:, 0], G=state[:, 1], info=info, slices=slices)
+
+
+def _loop_torch(K, s, U, state, info, tol, max_iter, rows):
+    """The loop of `smo_torch` on N variables with the signs `s` (P, N) int8
+    and the bounds `U` (P, N), from a given `state` (P, 2, N) and `info`.
+    `rows(t)`: the (P, N) rows of the variables `t` (P,); `K` gives the
+    diagonal."""
+    import torch
+    P, N = s.shape
+    dev = K.device
+    diag = K.diagonal().to(torch.float64)
+    diag = diag.repeat(N // len(diag))
+    sf = s.to(torch.float64)
+    pos = s > 0
+    alpha, G = state[:, 0], state[:, 1]
+    inf = torch.full((P, N), float('inf'), dtype=torch.float64, device=dev)
+    done = info[:, 0].clone()
+    status = info[:, 3] != 0
+    if not bool(torch.isfinite(diag).all()):
+        status[:] = True
+    col = torch.arange(P, device=dev)
+    looks = 0
+    while True:
+        v = -sf * G
+        up = torch.where(pos, alpha < U, alpha > 0)
+        low = torch.where(pos, alpha > 0, alpha < U)
+        m, i = torch.where(up, v, -inf).max(1)       # (the first on a tie)
+        M = torch.where(low, v, inf).min(1).values
+        status |= ~torch.isfinite(G).all(1)
+        run = ~status & ~(m - M < tol) & (done < max_iter)
+        looks += 1
+        if not bool(run.any()):
+            break
+        Ki = rows(i)
+        b = m[:, None] - v
+        a = (diag[i][:, None] + diag[None, :]) - 2.0 * Ki
+        a = torch.where(a <= 0, torch.full_like(a, TAU), a)
+        cand = low & (v < m[:, None])
+        obj = torch.where(cand, -(b * b) / a, inf)
+        none = ~cand.any(1) | torch.isnan(obj).any(1)
+        j = torch.where(torch.isnan(obj), inf, obj).argmin(1)
+        Kj = rows(j)
+        ai, aj = alpha[col, i], alpha[col, j]
+        ni, nj = _pair(ai, aj, G[col, i], G[col, j], U[col, i], U[col, j],
+                       s[col, i] != s[col, j], a[col, j])
+        status |= run & none
+        run &= ~none
+        zero = torch.zeros_like(ai)
+        si = torch.where(run, sf[col, i] * (ni - ai), zero)
+        sj = torch.where(run, sf[col, j] * (nj - aj), zero)
+        alpha[col, i] = torch.where(run, ni, ai)
+        alpha[col, j] = torch.where(run, nj, alpha[col, j])
+        G[:] = torch.where(run[:, None],
+                           G + sf * (Ki * si[:, None] + Kj * sj[:, None]), G)
+        done += run.to(torch.float64)
+    info[:, 0], info[:, 1], info[:, 2] = done, m, M
+    info[:, 3] = status.to(torch.float64)
+    return Result(alpha=alpha, G=G, info=info, slices=looks)
+
+
+def smo_torch_from(K, y, U, state, info, tol=1e-3, max_iter=1_000_000):
+    """`smo_torch` entered with a given `state` and `info` (advanced in
+    place)."""
+    import torch
+    n = K.shape[0]
+    P = _check_batch(y, U, n)
+    _check_limits(tol, max_iter)
+    K = K.to(torch.float64)
+    dev = K.device
+    state, info = _check_state(state, info, P, n, dev)
+    return _loop_torch(K, y.to(dev), U.to(dev), state, info, tol, max_iter,
+                       lambda t: K.index_select(0, t))
+
+
+def solve_from(K, y, U, state, info, tol, max_iter):
+    """(Result, fused?) from a given start: `smo_from` for a CUDA matrix of n
+    <= NMAX, `smo_torch_from` anywhere else."""
+    n = K.shape[0]
+    dev = K.device
+    if K.is_cuda and n <= NMAX:
+        if n > 1 and K.stride() not in ((n, 1), (1, n)) or K.data_ptr() % 16:
+            K = K.contiguous()
+        return smo_from(K, y.to(dev), U.to(dev), state, info, tol,
+                        max_iter), True
+    return smo_torch_from(K, y, U, state, info, tol, max_iter), False
+
+
+def one_class_start(K, nu, U):
+    """(state (P, 2, n) = [alpha0 | G0 = K alpha0], info (P, 4) = [0, inf,
+    -inf, 0]) of the one-class problems ``min 1/2 a^T K a``, ``0 <= a <= U``,
+    ``sum a = nu[p] l`` over the l members (``U > 0``) of row p, where K is:
+    libsvm's start on the members in index order, the first ``int(nu l)`` at
+    1 and the next at the remainder.  `G0` is one `svm_decide_*` launch with
+    zero intercepts on a CUDA matrix, `decide_torch` anywhere else.
+
+    K: (n, n) float32 or float64; nu: (P,) and U: (P, n) float64 tensors."""
+    import torch
+    if not torch.is_tensor(K) or K.dim() != 2 or K.shape[0] != K.shape[1] \
+            or K.dtype not in (torch.float32, torch.float64):
+        raise TypeError('K: (n, n) float32 or float64 expected')
+    n = K.shape[0]
+    P = _check_batch2(U, n)
+    if not torch.is_tensor(nu) or nu.dtype != torch.float64 \
+            or nu.shape != (P,):
+        raise TypeError(f'nu: ({P},) float64 expected')
+    nu, member = nu.cpu().numpy(), (U > 0).cpu().numpy()
+    if not np.all((nu > 0) & (nu <= 1)):
+        raise ValueError('nu: numbers in (0, 1] expected')
+    a0 = np.zeros((P, n))
+    for p in range(P):
+        idx = np.flatnonzero(member[p])
+        total = nu[p] * len(idx)
+        full = int(total)
+        a0[p, idx[:full]] = 1.0
+        if full < len(idx):
+            a0[p, idx[full]] = total - full
+    dev = K.device
+    state = torch.empty((P, 2, n), dtype=torch.float64, device=dev)
+    state[:, 0] = torch.from_numpy(a0).to(dev)
+    zero = torch.zeros(P, dtype=torch.float64, device=dev)
+    alpha0 = state[:, 0].contiguous()
+    state[:, 1] = decide(K, alpha0, zero) if K.is_cuda \
+        else decide_torch(K, alpha0, zero)
+    return state, _info0(P, dev)
+
+
+# -- 2n variables over the n samples: epsilon-SVR -----------------------------------
+_module2 = STATIC['svr.hip']
+#: the LDS budget of svr.hip: G and alpha of both variables of a sample
+NMAX2 = NMAX // 2
+
+
+def _check_batch2(U, n):
+    import torch
+    if not torch.is_tensor(U) or U.dtype != torch.float64 or U.dim() != 2 \
+            or U.shape[1] != n or U.shape[0] < 1:
+        raise TypeError(f'U: (P, {n}) float64 expected')
+    return U.shape[0]
+
+
+def start2(z, eps, device):
+    """(state (P, 2, 2n) = [alpha = 0 | G = (eps - z, eps + z)], info (P, 4) =
+    [0, inf, -inf, 0]) of a batch of epsilon-SVR problems before their first
+    step: the targets `z` (P, n) and the tube widths `eps` (P,) reach the
+    solver through G alone."""
+    import torch
+    if not torch.is_tensor(z) or z.dtype != torch.float64 or z.dim() != 2 \
+            or z.shape[0] < 1 or z.shape[1] < 1:
+        raise TypeError('z: (P, n) float64 expected')
+    P, n = z.shape
+    if not torch.is_tensor(eps) or eps.dtype != torch.float64 \
+            or eps.shape != (P,):
+        raise TypeError(f'eps: ({P},) float64 expected')
+    if not bool(torch.isfinite(z).all()) \
+            or not bool((torch.isfinite(eps) & (eps >= 0)).all()):
+        raise ValueError('z: finite numbers, eps: finite numbers >= 0 expected')
+    z, eps = z.to(device), eps.to(device)
+    state = torch.zeros((P, 2, 2 * n), dtype=torch.float64, device=device)
+    state[:, 1, :n] = eps[:, None] - z
+    state[:, 1, n:] = eps[:, None] + z
+    return state, _info0(P, device)
+
+
+def smo2_slice(K, U, state, info, tol, steps, max_iter):
+    """One launch of `svm_smo2_*`: at most `steps` steps of every problem that
+    has not stopped, on `state` (P, 2, 2n) and `info` in place."""
+    import torch
+    n = _check_K(K)
+    if n > NMAX2:
+        raise ValueError(f'n = {n}: at most NMAX2 = {NMAX2} on the fused '
+                         'path; see smo2_torch')
+    dev = K.device
+    P = _check_batch2(U, n)
+    _check_limits(tol, max_iter, steps)
+    if U.device != dev:
+        raise ValueError('K and U must be on the same device')
+    U = U.contiguous()
+    state = _f64('state', state, (P, 2, 2 * n), dev)
+    info = _f64('info', info, (P, 4), dev)
+    with torch.cuda.device(dev):
+        _module2.launch(f'svm_smo2_{suffix(K.dtype)}', P, _BLOCK, 'QiQQQdqq',
+                        K.data_ptr(), n, U.data_ptr(), state.data_ptr(),
+                        info.data_ptr(), float(tol), int(steps),
+                        int(max_iter), stream=current_stream(dev))
+    return state, info
+
+
+def smo2(K, U, z, eps, tol=1e-3, max_iter=1_000_000, steps=SLICE):
+    """The batch of epsilon-SVR problems solved by relaunching `svm_smo2_*`
+    until every problem has stopped: one download of `info` per launch,
+    nothing else.  `alpha` and `G` of the result are (P, 2n): a, then a*.
+
+    K: (n, n) float32 or float64 CUDA tensor, n <= NMAX2, symmetric,
+    contiguous along either index, 16-byte aligned (read as it lies).  U: (P,
+    n) the bound of both variables of a sample; z: (P, n); eps: (P,)."""
+    n = _check_K(K)
+    P = _check_batch2(U, n)
+    _check_limits(tol, max_iter, steps)
+    U = U.contiguous()
+    state, info = start2(z, eps, K.device)
+    if state.shape != (P, 2, 2 * n):
+        raise TypeError(f'z: ({P}, {n}) float64 expected')
+    slices = 0
+    while True:
+        smo2_slice(K, U, state, info, tol, steps, max_iter)
+        slices += 1
+        if stopped(info.cpu().numpy(), tol, max_iter).all():
+            break
+    return Result(alpha=state[:, 0], G=state[:, 1], info=info, slices=slices)
+
+
+def smo2_torch(K, U, z, eps, tol=1e-3, max_iter=1_000_000):
+    """The same rule with torch operations on any device, all problems
+    advancing together: variable t has the sign +1 below n and -1 from n on,
+    the bound ``U[t mod n]`` and the row ``K[t mod n]`` laid out twice."""
+    import torch
+    n = K.shape[0]
+    P = _check_batch2(U, n)
+    _check_limits(tol, max_iter)
+    K = K.to(torch.float64)
+    dev = K.device
+    state, info = start2(z, eps, dev)
+    if state.shape != (P, 2, 2 * n):
+        raise TypeError(f'z: ({P}, {n}) float64 expected')
+    s = torch.ones((P, 2 * n), dtype=torch.int8, device=dev)
+    s[:, n:] = -1
+    return _loop_torch(K, s, U.to(dev).repeat(1, 2), state, info, tol,
+                       max_iter, lambda t: K.index_select(0, t % n).repeat(1, 2))
+
+
+def solve2(K, U, z, eps, tol, max_iter):
+    """(Result, fused?): `smo2` for a CUDA matrix of n <= NMAX2, `smo2_torch`
+    anywhere else."""
+    n = K.shape[0]
+    if K.is_cuda and n <= NMAX2:
+        if n > 1 and K.stride() not in ((n, 1), (1, n)) or K.data_ptr() % 16:
+            K = K.contiguous()
+        return smo2(K, U.to(K.device), z, eps, tol, max_iter), True
+    return smo2_torch(K, U, z, eps, tol, max_iter), False
