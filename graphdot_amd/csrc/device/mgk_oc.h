@@ -50,6 +50,13 @@
 
 // -DGD_MARKS: phase names as comments in the ISA (scripts/isa_phases.py counts
 // the instructions between them)
+// -DGD_STAMPS: the clock at the ends of the phases, summed per launch behind
+// the iteration counters (scripts/phase_stamps.py) -- never in product kernels.
+#ifdef GD_STAMPS
+#define GD_OC_STAMP(k) (st_t[k] = __builtin_amdgcn_s_memtime())
+#else
+#define GD_OC_STAMP(k) ((void)0)
+#endif
 #ifdef GD_MARKS
 #define GD_MARK(name) asm volatile("; GDMARK " #name)
 #else
@@ -631,7 +638,11 @@ struct oc_solver {
                 job_sync<W>();
             }
         }
+#ifdef GD_STAMPS
+        unsigned long long st_t[6], st_acc[7] = {0, 0, 0, 0, 0, 0, 0};
+#endif
         for (unsigned t = blockIdx.x; t < prm.n_launch_jobs; t += gridDim.x) {
+            GD_OC_STAMP(0);
             const job_t job = scalar_load(prm.jobs + t);
             [[maybe_unused]] int no1 = 0, no2 = 0;     // QUOT: nodes of the full graphs
             graph_header_t h1 = load_header(headers + job.i, no1), h2 = load_header(headers + job.j, no2);
@@ -789,6 +800,7 @@ struct oc_solver {
             }
 
             GD_MARK(rectangles);
+            GD_OC_STAMP(1);
             // ---- degree histograms -> offsets of the degree-pair rectangles ---
             // (every wave computes the same wave-uniform numbers)
             if constexpr (!FLY) {
@@ -972,11 +984,36 @@ struct oc_solver {
                             }
                         }
                     }
+                    // QUOT: the table values of all the grid's cells, loaded
+                    // here in one go.  Left to the slot loop, the product with
+                    // gw1 gw2 makes the compiler sink load and product under a
+                    // branch on the cell's validity: one exposed round trip to
+                    // the table per slot.  Every half-term addresses a real
+                    // element (open_grid), so the loads need no guard; the
+                    // pins in the slot loop hold them above the selects.
+                    // ((16,4) in double sits at the 128 registers of its four
+                    // waves: every branch-free form tried spills 16 bytes more
+                    // than the 12 it has -- it keeps the loads of the loop)
+                    constexpr bool GPRE = QUOT && TAB && G0 > 0 &&
+                        !(sizeof(real) == 8 && G0 == 16 && S == 20 && R == 2);
+                    [[maybe_unused]] real gtab[GPRE ? G0 : 1];
+                    if constexpr (GPRE) {
+#pragma unroll
+                        for (int s = 0; s < G0; ++s)
+                            gtab[s] = at32(ketab, grid.t1[s / GV] + grid.t2[s % GV]);
+                    }
     #pragma unroll
                     for (int s = 0; s < S; ++s) {
                         // (limits the scheduler's hoisting of loads -- and with it the
                         // live registers -- to SETUP_CHUNK slots)
                         if (s % SETUP_CHUNK == 0) __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (GPRE) {
+                            if (s < G0 && s % SETUP_CHUNK == 0) {
+#pragma unroll
+                                for (int u = s; u < s + SETUP_CHUNK && u < G0; ++u)
+                                    asm volatile("" : "+v"(gtab[u]));
+                            }
+                        }
                         real e;
                         bool ok;
                         unsigned col;
@@ -984,7 +1021,8 @@ struct oc_solver {
                             const int gu = s / GV, gv = s % GV;
                             ok = grid.u[gu] && grid.v[gv];
                             if constexpr (TAB) {
-                                e = at32(ketab, grid.t1[gu] + grid.t2[gv]);
+                                if constexpr (GPRE) e = gtab[s];
+                                else e = at32(ketab, grid.t1[gu] + grid.t2[gv]);
                                 if constexpr (GD_WEIGHTED && edge_weight<edge_t>::value)
                                     e *= real(edge_weight<edge_t>::get(ge1[gu])) *
                                          real(edge_weight<edge_t>::get(ge2[gv]));
@@ -1108,6 +1146,7 @@ struct oc_solver {
             }
 
             GD_MARK(rows);
+            GD_OC_STAMP(2);
             // ---- rows owned by this thread (sorted order) ----------------------
             real dg[R], mi[R], r[CW][R], p[CW][R];
             real x[C][KEEP_X ? R : 1];
@@ -1413,6 +1452,7 @@ struct oc_solver {
                     for (int s_ = 0; s_ < S; ++s_) asm volatile("" : "+v"(val[s_]), "+v"(adr[s_]));
                 }
                 GD_MARK(cg_loop);
+                GD_OC_STAMP(3);
                 // (the reference stops after N iterations at the latest -- where CG
                 // in exact arithmetic has the solution.  With step lengths rounded
                 // to float (FSCAL) a system of one or two rows is left with the
@@ -1709,6 +1749,7 @@ struct oc_solver {
             }
             if constexpr (SEQ) it = (it + 1u) / 2u;   // (iterations per system)
             GD_MARK(epilogue);
+            GD_OC_STAMP(4);
             if (prm.iters != nullptr && tid == 0) prm.iters[prm.order[t]] = it;
             if constexpr (LEAN) {
 #pragma unroll
@@ -2368,7 +2409,24 @@ struct oc_solver {
                     }
                 }
             }
+#ifdef GD_STAMPS
+            GD_OC_STAMP(5);
+            st_acc[0] += st_t[3] - st_t[0];     // set-up
+            st_acc[1] += st_t[4] - st_t[3];     // CG loop
+            st_acc[2] += st_t[5] - st_t[4];     // epilogue
+            st_acc[3] += 1;
+            st_acc[4] += st_t[1] - st_t[0];     // set-up: stage
+            st_acc[5] += st_t[2] - st_t[1];     //         rectangles, rowmap, slots
+            st_acc[6] += st_t[3] - st_t[2];     //         rows
+#endif
         }
+#ifdef GD_STAMPS
+        if (tid == 0 && prm.iters != nullptr) {
+            unsigned long long *acc = reinterpret_cast<unsigned long long *>(
+                prm.iters + ((prm.nX * prm.nY + 1) & ~1u));   // behind the per-job counters
+            for (int k = 0; k < 7; ++k) atomicAdd(acc + k, st_acc[k]);
+        }
+#endif
     }
 
     // the first array if B, else the second (their extents differ)

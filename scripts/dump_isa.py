@@ -8,6 +8,7 @@
 --maximin / --m3: the fused epilogue flavours of the owner-computes solvers
 (nodal value solve, direct microkernel evaluation; --m3 needs --f64).
 """
+import hashlib
 import os
 import subprocess
 import sys
@@ -56,7 +57,11 @@ else:
                                 tab=2 if '--tab=2' in sys.argv else '--tab' in sys.argv,
                                 weighted=dgs[0].weighted,
                                 quot='--quot' in sys.argv)
-path = f'/tmp/_dump_isa_{W}_{S}_{R}_{C}_{int(real is np.float64)}_{flavour}.hip'
+# (a name of its own per variant and set of flags: callers run several dumps
+# side by side)
+tag = hashlib.sha1(' '.join(sys.argv[1:] + [os.environ.get('GD_HIPCC_EXTRA', '')])
+                   .encode()).hexdigest()[:12]
+path = f'/tmp/_dump_isa_{tag}.hip'
 open(path, 'w').write(src)
 flags = [f for f in jit.BASE_FLAGS if f != '--genco'] + \
     os.environ.get('GD_HIPCC_EXTRA', '').split()
