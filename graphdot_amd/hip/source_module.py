@@ -87,6 +87,7 @@ STATIC_SOURCES = (
     'model/clustering/lloyd.hip',
     'model/svm/smo.hip',
     'model/svm/svr.hip',
+    'model/alignment/alignment.hip',
 )
 #: file name -> SourceModule
 STATIC = {os.path.basename(p): SourceModule(os.path.join(_PACKAGE, p))
