@@ -598,6 +598,24 @@ struct oc_solver {
         int i1, i2, rs1, rs2, d1, d2, prod;
     };
     constexpr static int GQU = QUOT ? GU : 1, GQV = QUOT ? GV : 1;
+    // RECS: the one-pass set-up of the double quotient kernels with tables
+    // takes a half-term -- one nonzero of one graph on one side of a slot --
+    // from ONE 16-byte record of the graph's `terms` section
+    // (_devicegraph.term_bytes: written once per arena, in front of the class
+    // section) instead of the chain nz -> edge class, scale(i), scale(j) and
+    // their product: {f64 qw = s(i) s(j); f32 w; u16 j; u8 class; u8 0}.  qw
+    // is the IEEE product `qweight` forms, so the slot values keep their
+    // bits.  (Float kernels multiply the scales rounded to float: they, and
+    // the two-pass set-up, keep the sections and skip the records when they
+    // stage an image.)
+    constexpr static bool RECS = QUOT && TAB && ONE_PASS && sizeof(real) == 8;
+    typedef unsigned term_t __attribute__((ext_vector_type(4)));
+    __device__ static __forceinline__ double term_qw(term_t const &t) {
+        const unsigned long long bits = ((unsigned long long)t.y << 32) | t.x;
+        return __builtin_bit_cast(double, bits);
+    }
+    __device__ static __forceinline__ unsigned term_j(term_t const &t) { return t.w & 0xFFFFu; }
+    __device__ static __forceinline__ unsigned term_cls(term_t const &t) { return (t.w >> 16) & 0xFFu; }
     struct grid_t {       // GRID: the first batch's row as GU + GV half-terms
         unsigned a[GU], b[GV];        // element indices (clamped into the row)
         unsigned j1[GU], j2[GV];      // lp byte address = j1[u] + j2[v]
@@ -672,16 +690,19 @@ struct oc_solver {
             const unsigned nzpad1 = ((unsigned)n1 + 3u) & ~3u, nzpad2 = ((unsigned)n2 + 3u) & ~3u;
             const unsigned cb1 = TAB ? (nzpad1 + (((unsigned)h1.n_nz + 3u) & ~3u) + 15u) & ~15u : 0u;
             const unsigned cb2 = TAB ? (nzpad2 + (((unsigned)h2.n_nz + 3u) & ~3u) + 15u) & ~15u : 0u;
+            // RECS: the records in front of the class section, staged with it
+            const unsigned tb1 = RECS ? 16u * (unsigned)h1.n_nz : 0u, tb2 = RECS ? 16u * (unsigned)h2.n_nz : 0u;
+            const unsigned pre1 = cb1 + tb1, pre2 = cb2 + tb2;
 
             GD_MARK(stage);
             // ---- stage both graph images in LDS: one global round trip --------
             job_sync<W>();  // previous pair is done with the LDS regions
             {
                 typedef unsigned v4 __attribute__((ext_vector_type(4)));
-                const unsigned w1 = (h1.perm + 2u * n1 - h1.degree + cb1 + 15u) / 16u;
-                const unsigned w2 = (h2.perm + 2u * n2 - h2.degree + cb2 + 15u) / 16u;
-                const v4 *const s1 = reinterpret_cast<const v4 *>(prm.arena + h1.degree - cb1);
-                const v4 *const s2 = reinterpret_cast<const v4 *>(prm.arena + h2.degree - cb2);
+                const unsigned w1 = (h1.perm + 2u * n1 - h1.degree + pre1 + 15u) / 16u;
+                const unsigned w2 = (h2.perm + 2u * n2 - h2.degree + pre2 + 15u) / 16u;
+                const v4 *const s1 = reinterpret_cast<const v4 *>(prm.arena + h1.degree - pre1);
+                const v4 *const s2 = reinterpret_cast<const v4 *>(prm.arena + h2.degree - pre2);
                 v4 *const d1 = reinterpret_cast<v4 *>(lG1);
                 v4 *const d2 = reinterpret_cast<v4 *>(lG2);
                 constexpr int K = 2;
@@ -710,14 +731,16 @@ struct oc_solver {
                         for (int c = 0; c < C; ++c) lY[(k * T + tid) * C + c] = 0;
                 }
             }
-            const Graph g1 = view_graph(lG1 + cb1 - h1.degree, h1, no1);
-            const Graph g2 = view_graph(lG2 + cb2 - h2.degree, h2, no2);
+            const Graph g1 = view_graph(lG1 + pre1 - h1.degree, h1, no1);
+            const Graph g2 = view_graph(lG2 + pre2 - h2.degree, h2, no2);
+            [[maybe_unused]] term_t const *const terms1 = reinterpret_cast<term_t const *>(lG1);
+            [[maybe_unused]] term_t const *const terms2 = reinterpret_cast<term_t const *>(lG2);
             // QUOT: s(i) s(j) of nonzero z of graph g
             [[maybe_unused]] auto qweight = [](Graph const &g, nz_t z) -> real {
                 return real(at32(g.scale, (unsigned)z.i)) * real(at32(g.scale, (unsigned)z.j));
             };
-            std::uint8_t const *const ncls1 = reinterpret_cast<std::uint8_t const *>(lG1);
-            std::uint8_t const *const ncls2 = reinterpret_cast<std::uint8_t const *>(lG2);
+            std::uint8_t const *const ncls1 = reinterpret_cast<std::uint8_t const *>(lG1) + tb1;
+            std::uint8_t const *const ncls2 = reinterpret_cast<std::uint8_t const *>(lG2) + tb2;
             std::uint8_t const *const ecls1 = ncls1 + nzpad1;
             std::uint8_t const *const ecls2 = ncls2 + nzpad2;
             const unsigned nvc = prm.n_vclass, nec = prm.n_eclass;
@@ -896,7 +919,9 @@ struct oc_solver {
             };
 
             // GRID: the first batch's row as GU + GV half-terms
-            auto open_grid = [&](unsigned base, unsigned elem) -> grid_t {
+            // (RECS: s(i) s(j) of the half-terms go to qw1[GU], qw2[GV])
+            auto open_grid = [&](unsigned base, unsigned elem, [[maybe_unused]] real *qw1 = nullptr,
+                                 [[maybe_unused]] real *qw2 = nullptr) -> grid_t {
                 const row_t r = open_row(0);
                 const bool live = r.prod > 0;
                 grid_t g;
@@ -910,6 +935,18 @@ struct oc_solver {
                     if (k < GV) g.v[k] = k < r.d2;
                     g.a[k] = live ? (unsigned)r.rs1 + (g.u[k] ? (unsigned)k : 0u) : 0u;
                     if (k < GV) g.b[k] = live ? (unsigned)r.rs2 + (g.v[k] ? (unsigned)k : 0u) : 0u;
+                    if constexpr (RECS) {
+                        const term_t r1 = at32(terms1, g.a[k]), r2 = at32(terms2, k < GV ? g.b[k] : 0u);
+                        g.j1[k] = base + __umul24(term_j(r1), (unsigned)ldp) * elem;
+                        g.t1[k] = __umul24(term_cls(r1), nec);
+                        qw1[k] = term_qw(r1);
+                        if (k < GV) {
+                            g.j2[k] = term_j(r2) * elem;
+                            g.t2[k] = term_cls(r2);
+                            qw2[k] = term_qw(r2);
+                        }
+                        continue;
+                    }
                     const nz_t z1 = at32(g1.nz, g.a[k]), z2 = at32(g2.nz, k < GV ? g.b[k] : 0u);
                     g.j1[k] = base + __umul24((unsigned)z1.j, (unsigned)ldp) * elem;
                     if (k < GV) g.j2[k] = (unsigned)z2.j * elem;
@@ -967,9 +1004,11 @@ struct oc_solver {
                     [[maybe_unused]] grid_t grid;
                     [[maybe_unused]] edge_t ge1[GU], ge2[GV];
                     [[maybe_unused]] real gw1[GQU], gw2[GQV];     // QUOT: s(i) s(j) of the half-terms
+                    [[maybe_unused]] bool wok[SETUP_CHUNK];       // RECS: validity of the chunk's walk slots
                     if constexpr (G0 > 0) {
-                        grid = open_grid(lp_off, ELEM);
-                        if constexpr (QUOT) {
+                        if constexpr (RECS) grid = open_grid(lp_off, ELEM, gw1, gw2);
+                        else grid = open_grid(lp_off, ELEM);
+                        if constexpr (QUOT && !RECS) {
 #pragma unroll
                             for (int k = 0; k < GU; ++k) {
                                 gw1[k] = qweight(g1, at32(g1.nz, grid.a[k]));
@@ -1038,6 +1077,17 @@ struct oc_solver {
                         } else {
                         ok = cur.valid();
                         const unsigned a = cur.a(), b = cur.e2;
+                        if constexpr (RECS) {
+                            // both half-terms of a walk slot from their records
+                            const term_t r1 = at32(terms1, a), r2 = at32(terms2, b);
+                            e = at32(ketab, __umul24(term_cls(r1), nec) + term_cls(r2));
+                            if constexpr (GD_WEIGHTED && edge_weight<edge_t>::value)
+                                e *= real(edge_weight<edge_t>::get(at32(g1.edge, a))) *
+                                     real(edge_weight<edge_t>::get(at32(g2.edge, b)));
+                            e *= term_qw(r1) * term_qw(r2);
+                            col = ok ? __umul24(term_j(r1), (unsigned)ldp) + term_j(r2) : 0u;
+                            col = lp_off + col * ELEM;
+                        } else {
                         const nz_t z1 = at32(g1.nz, a), z2 = at32(g2.nz, b);
                         if constexpr (TAB) {
                             e = at32(ketab, __umul24((unsigned)ecls1[a], nec) + ecls2[b]);
@@ -1052,8 +1102,17 @@ struct oc_solver {
                         col = ok ? __umul24((unsigned)z1.j, (unsigned)ldp) + (unsigned)z2.j : 0u;
                         col = lp_off + col * ELEM;
                         }
+                        }
                         if (SL > 0 && s >= SREG) {
                             lV[(s - SREG) * T + tid] = ok ? e : real(0);
+                        } else if (RECS && s >= G0) {
+                            // (selected at the end of the chunk, behind a pin:
+                            // a select right here lets the compiler sink the
+                            // record reads and the table load under a branch on
+                            // `ok`, one exposed round trip per slot -- every
+                            // lane addresses a real element, as in the grid)
+                            val[s] = e;
+                            wok[s % SETUP_CHUNK] = ok;
                         } else {
                             val[s] = ok ? e : real(0);
                         }
@@ -1065,6 +1124,15 @@ struct oc_solver {
                             adr[s] = col;
                         }
                         if (s % SETUP_CHUNK == SETUP_CHUNK - 1 || s == S - 1) {
+                            if constexpr (RECS) {
+#pragma unroll
+                                for (int u = s - s % SETUP_CHUNK; u <= s; ++u) {
+                                    if (u >= G0 && !(SL > 0 && u >= SREG)) {
+                                        asm volatile("" : "+v"(val[u]));
+                                        val[u] = wok[u % SETUP_CHUNK] ? val[u] : real(0);
+                                    }
+                                }
+                            }
 #pragma unroll
                             for (int u = s - s % SETUP_CHUNK; u <= s; ++u) {
                                 if (SL > 0 && u >= SREG) {

@@ -687,8 +687,13 @@ int gdh_gather_section(const uint8_t *blob, const int64_t *blob_off, const int64
 int gdh_assemble_arena(int64_t G, const uint8_t *blob, const int64_t *blob_off,
                        const int64_t *starts, const int64_t *cbytes, const int64_t *n_node,
                        const int64_t *n_nz, const uint8_t *ncls, const uint8_t *ecls,
-                       uint8_t *host, int64_t host_bytes) try {
+                       const int64_t *term_off, int32_t edge_size, int32_t weight_off,
+                       int32_t weight_size, uint8_t *host, int64_t host_bytes) try {
     if (G < 0) return -1;
+    if (term_off && (!ncls || !ecls || edge_size < 0 ||
+                     (weight_off >= 0 && ((weight_size != 4 && weight_size != 8) ||
+                                          weight_off + weight_size > edge_size))))
+        return -1;
     int64_t vn = 0, ve = 0;
     for (int64_t g = 0; g < G; ++g) {
         const int64_t nb = blob_off[g + 1] - blob_off[g];
@@ -700,6 +705,42 @@ int gdh_assemble_arena(int64_t G, const uint8_t *blob, const int64_t *blob_off,
             if (npad + n_nz[g] > cbytes[g]) return -2;
             std::memcpy(c0, ncls + vn, (size_t)n_node[g]);
             std::memcpy(c0 + npad, ecls + ve, (size_t)n_nz[g]);
+        }
+        if (term_off) {
+            // the half-term records of the quotient solver, in front of the classes
+            const int64_t nz_n = n_nz[g], first = starts[g] - cbytes[g] - 16 * nz_n;
+            const int64_t *off = term_off + 3 * g;
+            if (first < 0 || off[0] < 0 || off[1] < 0 || off[2] < 0 ||
+                off[0] + 8 * n_node[g] > nb || off[1] + 4 * nz_n > nb ||
+                off[2] + (int64_t)edge_size * nz_n > nb)
+                return -2;
+            const uint8_t *src = blob + blob_off[g];
+            uint8_t *out = host + first;
+            for (int64_t e = 0; e < nz_n; ++e, out += 16) {
+                uint16_t ij[2];
+                std::memcpy(ij, src + off[1] + 4 * e, 4);
+                if (ij[0] >= n_node[g] || ij[1] >= n_node[g]) return -2;
+                double si, sj;
+                std::memcpy(&si, src + off[0] + 8 * (int64_t)ij[0], 8);
+                std::memcpy(&sj, src + off[0] + 8 * (int64_t)ij[1], 8);
+                const double q = si * sj;      // rounded once, as on the device
+                float w = 1.0f;
+                if (weight_off >= 0) {
+                    const uint8_t *rec = src + off[2] + (int64_t)edge_size * e + weight_off;
+                    if (weight_size == 4) {
+                        std::memcpy(&w, rec, 4);
+                    } else {
+                        double wd;
+                        std::memcpy(&wd, rec, 8);
+                        w = (float)wd;
+                    }
+                }
+                const uint8_t tail[2] = {ecls[ve + e], 0};
+                std::memcpy(out, &q, 8);
+                std::memcpy(out + 8, &w, 4);
+                std::memcpy(out + 12, &ij[1], 2);
+                std::memcpy(out + 14, tail, 2);
+            }
         }
         vn += n_node[g];
         ve += n_nz[g];

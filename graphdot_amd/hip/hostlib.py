@@ -31,7 +31,7 @@ SIGNATURES = {
     'gdh_order_jobs': [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp],
     'gdh_pairwise_jobs': [_i64, _i64, _vp],
     'gdh_gather_section': [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64],
-    'gdh_assemble_arena': [_i64] + [_vp] * 9 + [_i64],
+    'gdh_assemble_arena': [_i64] + [_vp] * 9 + [_i32] * 3 + [_vp, _i64],
     'gdh_quotient_graph': [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32,
                            _vp, _vp, _i64, _vp, _vp],
 }
@@ -246,15 +246,27 @@ def gather_section(blob, blob_off, sec_off, col, count, dtype):
 
 
 def assemble_arena(blob, blob_off, starts, cbytes, n_node, n_nz, ncls, ecls,
-                   host):
+                   host, term_off=None, edge_t=None):
     """Blobs (and label-class sections) of a packed batch into the arena
-    image `host` (uint8)."""
+    image `host` (uint8).  `term_off` (quotient images: blob-relative offsets
+    of the sections scale, nz, edge of every graph, (G, 3)) and the edge
+    record type `edge_t`: also the `terms` sections in front of the classes
+    (_devicegraph.TERM_DTYPE)."""
+    edge_size, weight_off, weight_size = 0, -1, 0
+    if term_off is not None:
+        edge_t = np.dtype(edge_t)
+        edge_size = edge_t.itemsize
+        if edge_t.names and 'weight' in edge_t.names:
+            weight_off = edge_t.fields['weight'][1]
+            weight_size = edge_t.fields['weight'][0].itemsize
     _check(lib().gdh_assemble_arena(
         len(starts), _p(blob), _p(_c(blob_off, np.int64)),
         _p(_c(starts, np.int64)), _p(_c(cbytes, np.int64)),
         _p(_c(n_node, np.int64)), _p(_c(n_nz, np.int64)),
         None if ncls is None else _p(_c(ncls, np.uint8)),
         None if ecls is None else _p(_c(ecls, np.uint8)),
+        None if term_off is None else _p(_c(term_off, np.int64)),
+        edge_size, weight_off, weight_size,
         _p(host), host.nbytes), 'gdh_assemble_arena')
 
 

@@ -26,6 +26,7 @@ from ...microkernel import TensorProduct, Product
 from ...util.iterable import flatten, fold_like
 from ._backend import Backend
 from ._devicegraph import (DeviceGraph, GraphArena, HIST_BINS, class_bytes,
+                           term_bytes,
                            degree_histograms, graph_features, pack_many,
                            quotient_graph)
 
@@ -735,8 +736,11 @@ class HIPBackend(Backend):
 
     def _host_arena(self, dgraphs, fields):
         # (label classes are only numbered when the tables are in use)
+        # (and the half-term records of quotient images only for the solvers
+        # that read them: mgk_oc.h RECS, double)
         return GraphArena(dgraphs, *fields, classes=bool(self.tables),
-                          native=self.native)
+                          native=self.native,
+                          terms=np.dtype(self.real) == np.float64)
 
     def _arena(self, dgraphs, fields=(None, None)):
         key = (_ids(dgraphs), fields if self.tables else None)
@@ -1568,6 +1572,11 @@ void ${name}(params_t prm) {
         gbytes = np.maximum(image[ji], image[jj])
         # the owner-computes solvers with global tables stage the class ids
         image_oc = image + class_bytes(n_node, n_nz) if gtab else image
+        # ... and, in double, the half-term records of quotient images (the
+        # one-pass set-up reads them, mgk_oc.h RECS; sized for every variant)
+        if (gtab and np.dtype(self.real) == np.float64 and len(dgraphs)
+                and getattr(dgraphs[0], 'n_orig', None) is not None):
+            image_oc = image_oc + term_bytes(n_nz)
         gbytes_oc = np.maximum(image_oc[ji], image_oc[jj])
         maxdeg = f['max_degree']
         pair_maxdeg = np.maximum(maxdeg[ji], maxdeg[jj])

@@ -906,6 +906,21 @@ def class_bytes(n_node, n_nz):
         // _ALIGN * _ALIGN
 
 
+#: one record of the `terms` section of a quotient arena (GraphArena): what the
+#: quotient solver needs of one nonzero (i, j) of a graph on one side of a
+#: slot -- qw = scale[i] * scale[j] (the float64 product), the edge's weight
+#: (1 in unweighted graphs), the column j and the edge's class id
+TERM_DTYPE = np.dtype([('qw', np.float64), ('w', np.float32),
+                       ('j', np.uint16), ('cls', np.uint8), ('pad', np.uint8)])
+
+
+def term_bytes(n_nz):
+    """Bytes of the `terms` section that precedes the class section of a
+    graph in a quotient arena with numbered labels: one TERM_DTYPE record per
+    nonzero.  mgk_oc.h (RECS) computes the same."""
+    return np.asarray(n_nz) * TERM_DTYPE.itemsize
+
+
 def _label_classes(dgraphs, vfields=None, efields=None, max_classes=255,
                    native=True):
     """Number the distinct node records and the distinct edge *labels* (the
@@ -1029,10 +1044,19 @@ class GraphArena:
     The class section of a graph (`class_bytes`) sits directly in front of
     its blob so that the solver stages [classes | degree .. perm] into LDS
     with one contiguous copy.  `classes` is None when the labels cannot be
-    numbered (`_label_classes`); the sections are then zero."""
+    numbered (`_label_classes`); the sections are then zero.
+
+    An arena of quotient images (`quotient_graph`) whose labels were numbered
+    also carries, unless `terms` is False, a section `terms` per graph in
+    front of its classes -- [terms g][classes g][blob g], `term_bytes` --:
+    one TERM_DTYPE record per nonzero, in nz order.  It holds what depends on
+    one graph and the class numbering only, made once here instead of once
+    per pair and slot in the solver (mgk_oc.h RECS).
+    `term_bytes` is zero for every other arena: full images keep their
+    layout byte for byte."""
 
     def __init__(self, dgraphs, vfields=None, efields=None, classes=True,
-                 native=True):
+                 native=True, terms=True):
         self.n = len(dgraphs)
         hdr_bytes = _pad(self.n * HEADER_DTYPE.itemsize)
         cls = _label_classes(dgraphs, vfields, efields, native=native) \
@@ -1051,12 +1075,17 @@ class GraphArena:
                                             dtype=np.int64)
         cbytes = class_bytes(feat['n_node'], feat['n_nz']) \
             if self.n else np.zeros(0, np.int64)
-        ends = cursor + np.cumsum(sizes + cbytes)
+        with_terms = bool(terms and cls is not None and self.n and getattr(
+            dgraphs[0], 'n_orig', None) is not None)
+        tbytes = term_bytes(feat['n_nz']) if with_terms \
+            else np.zeros(self.n, np.int64)
+        ends = cursor + np.cumsum(sizes + cbytes + tbytes)
         starts = ends - sizes if self.n else np.zeros(0, np.int64)
         self.nbytes = int(ends[-1]) if self.n else int(cursor)
         self.host = np.zeros(self.nbytes, dtype=np.uint8)
         self.blob_start = starts
         self.class_bytes = cbytes
+        self.term_bytes = tbytes
         if cls is not None:
             c = self.classes
             self.host[c['vrep']:c['vrep'] + vrep.nbytes] = \
@@ -1065,8 +1094,20 @@ class GraphArena:
                 erep.view(np.uint8).ravel() if erep.nbytes else []
         self._relocs = []
         hdr = np.zeros(self.n, dtype=HEADER_DTYPE)
-        natively = native and b0 is not None and self.n > 0
-        if natively:
+        natively = native and self.n > 0 and (b0 is not None or with_terms)
+        if natively and with_terms:
+            # (quotient images are packed one by one: back to back they take
+            # the native pass like a batch, which also writes their terms)
+            from ...hip import hostlib
+            hostlib.assemble_arena(
+                np.concatenate([g.blob for g in dgraphs]),
+                np.concatenate(([0], np.cumsum(sizes))), starts, cbytes,
+                feat['n_node'], feat['n_nz'], ncls, ecls, self.host,
+                term_off=np.array(
+                    [[g.offsets[s] for s in ('scale', 'nz', 'edge')]
+                     for g in dgraphs], dtype=np.int64),
+                edge_t=dgraphs[0].edge_t)
+        elif natively:
             # blobs and class sections in one native pass (gdh_assemble_arena)
             from ...hip import hostlib
             hostlib.assemble_arena(
@@ -1114,6 +1155,22 @@ class GraphArena:
                 nz0 = np.cumsum(n_nz) - n_nz
                 self.host[np.repeat(c1 - nz0, n_nz)
                           + np.arange(int(n_nz.sum()))] = ecls
+                if with_terms:
+                    # (the specification gdh_assemble_arena is held to)
+                    edge_t = np.dtype(dgraphs[0].edge_t)
+                    for k, g in enumerate(dgraphs):
+                        rec = np.zeros(g.n_nz, dtype=TERM_DTYPE)
+                        zi, zj = g.nz['i'].astype(np.int64), g.nz['j']
+                        rec['qw'] = g.scale[zi] * g.scale[zj.astype(np.int64)]
+                        rec['w'] = 1
+                        if g.weighted:
+                            o = g.offsets['edge']
+                            rec['w'] = g.blob[o:o + g.n_nz * edge_t.itemsize] \
+                                .view(edge_t)['weight']
+                        rec['j'] = zj
+                        rec['cls'] = ecls[nz0[k]:nz0[k] + g.n_nz]
+                        at = int(c0[k] - tbytes[k])
+                        self.host[at:at + rec.nbytes] = rec.view(np.uint8)
         self._hdr = hdr
         self._relocs = (np.concatenate(self._relocs) if self._relocs
                         else np.zeros(0, np.int64))

@@ -141,11 +141,21 @@ int gdh_gather_section(const uint8_t *blob, const int64_t *blob_off, const int64
  * of a packed batch goes to host + starts[g], and -- when ncls / ecls are
  * given -- the u8 label classes of its nodes (pad4) and nonzeros to the
  * cbytes[g] bytes in front of it.  ncls / ecls: the classes of all graphs
- * back to back. */
+ * back to back.
+ * term_off (quotient images with classes, else NULL): per graph the
+ * blob-relative offsets of its sections scale, nz and edge, [3 g + 0 .. 2].
+ * The `terms` section then goes in front of the classes, at host + starts[g]
+ * - cbytes[g] - 16 n_nz[g]: one 16-byte record per nonzero e = (i, j), in nz
+ * order -- {f64 qw = scale[i] * scale[j] (the product rounded once, in
+ * double); f32 w = the edge's weight (edge_size bytes per edge record, the
+ * weight a float of weight_size bytes at weight_off; weight_off < 0: 1.0f);
+ * u16 j; u8 class of e; u8 0} -- what the quotient solver reads per
+ * half-term of a slot (mgk_oc.h RECS). */
 int gdh_assemble_arena(int64_t G, const uint8_t *blob, const int64_t *blob_off,
                        const int64_t *starts, const int64_t *cbytes, const int64_t *n_node,
                        const int64_t *n_nz, const uint8_t *ncls, const uint8_t *ecls,
-                       uint8_t *host, int64_t host_bytes);
+                       const int64_t *term_off, int32_t edge_size, int32_t weight_off,
+                       int32_t weight_size, uint8_t *host, int64_t host_bytes);
 
 /* The job list of a kernel-matrix evaluation, (u32 i, u32 j) per pair in
  * row-major order: ny < 0: the upper triangle of an nx x nx symmetric matrix
