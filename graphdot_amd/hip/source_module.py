@@ -88,6 +88,7 @@ STATIC_SOURCES = (
     'model/svm/smo.hip',
     'model/svm/svr.hip',
     'model/alignment/alignment.hip',
+    'model/two_sample/mmd.hip',
 )
 #: file name -> SourceModule
 STATIC = {os.path.basename(p): SourceModule(os.path.join(_PACKAGE, p))
