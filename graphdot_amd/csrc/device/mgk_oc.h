@@ -85,8 +85,38 @@ template<int DMAX> struct class_order {
     }
 };
 
+// class_order by lane, for the kernels that lay out the rectangles per lane
+// (oc_solver LANE_TABS; NCP <= 32).  The K-th rectangle of the order sits in
+// lane 32 - NCP + K: `a1` and `a2` are the byte offsets of the lanes it reads
+// its two counts from (lane d1 and lane 16 + d2), `cell` the byte offset of
+// its cell d1 * NC + d2 of `tab_off`.  Every other lane reads lane 48 twice,
+// a zero, and owns one of the cells from NCP on: with the rectangles at the
+// top of the first 32 lanes the prefix sum of the sizes is 0 in all of them
+// (nothing below lanes 0.., and rows 2 and 3 take nothing from rows 0 and 1).
+template<int DMAX> struct rectangle_lanes {
+    unsigned char a1[64], a2[64], cell[64];
+    constexpr rectangle_lanes() : a1{}, a2{}, cell{} {
+        constexpr class_order<DMAX> ord{};
+        constexpr int NC = DMAX + 1, NCP = NC * NC, L0 = 32 - NCP;
+        int spare = NCP;
+        for (int l = 0; l < 64; ++l) {
+            const int k = l - L0;
+            if (k >= 0 && k < NCP) {
+                a1[l] = (unsigned char)(4 * ord.d1[k]);
+                a2[l] = (unsigned char)(4 * (16 + ord.d2[k]));
+                cell[l] = (unsigned char)(4 * (ord.d1[k] * NC + ord.d2[k]));
+            } else {
+                a1[l] = a2[l] = 4 * 48;
+                cell[l] = (unsigned char)(4 * spare++);
+            }
+        }
+    }
+};
+
 // Table layout (reals): [kv: nv^2][ke: ne^2], and for C == 2 behind them
-// [dkv_j: nv^2 for each node hyperparameter j][dke_j: ne^2 for each edge one].
+// [dkv_j: nv^2 for each node hyperparameter j][dke_j: ne^2 for each edge one];
+// for C == 1 behind them [1 / (1 - q)^2][q^2 / q0^2], the scalars of the
+// evaluation (the host sizes every table buffer two reals longer).
 // The representatives of the edge classes carry weight 1: tables hold the
 // label part, weights are applied per nonzero.
 template<class real, int C, class Graph, class NodeK, class EdgeK, class PStart>
@@ -99,6 +129,16 @@ __device__ __forceinline__ void fill_tables(params_t<real, Graph, NodeK, EdgeK, 
     const unsigned nvv = nv * nv, nee = ne * ne;
     real *const kv = prm.tables, *const ke = kv + nvv;
     real *const dkv = ke + nee, *const dke = dkv + (size_t)NodeK::jac_dims * nvv;
+    if constexpr (C == 1) {
+        // the scalars of the evaluation behind the value tables: the
+        // expressions of oc_solver::run, which the quotient solvers read from
+        // here (EVSC) instead of dividing twice per pair
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const real q = prm.q, q0 = prm.q0;
+            ke[nee] = real(1) / ((real(1) - q) * (real(1) - q));
+            ke[nee + 1] = q * q / (q0 * q0);
+        }
+    }
     for (unsigned k = blockIdx.x * blockDim.x + threadIdx.x; k < nvv + nee; k += gridDim.x * blockDim.x) {
         if (k < nvv) {
             const unsigned c1 = k / nv, c2 = k - c1 * nv;
@@ -525,6 +565,7 @@ struct oc_solver {
     constexpr static int off_v = off_q + 1;
     constexpr static int off_e = off_v + NodeK::jac_dims;
     constexpr static class_order<DMAX> ORD{};
+    constexpr static rectangle_lanes<(DMAX < 4 ? DMAX : 4)> RECT{};
 
     struct lds_t {
         real red[2][2 * W];     // two halves: see alternating_reduce
@@ -609,6 +650,17 @@ struct oc_solver {
     // the two-pass set-up, keep the sections and skip the records when they
     // stage an image.)
     constexpr static bool RECS = QUOT && TAB && ONE_PASS && sizeof(real) == 8;
+    // QSET: set-up work of the one-wave quotient kernels that does not depend
+    // on the pair, or only through a few integers, is taken off the vector
+    // pipe ("set-up scalars"): the output addresses
+    // come by scalar loads next to the headers, the staging loads carry no
+    // per-lane guard, and the rectangle tables are computed per lane
+    // (LANE_TABS) instead of on the scalar unit with one lane write each.
+    // EVSC: 1 / (1 - q)^2 and q^2 / q0^2 are read from behind the tables,
+    // where `fill_tables` leaves them once per evaluation.
+    constexpr static bool QSET = QUOT && W == 1;
+    constexpr static bool EVSC = QSET && TAB;
+    constexpr static bool LANE_TABS = QSET && !FLY && NCP <= 32;
     typedef unsigned term_t __attribute__((ext_vector_type(4)));
     __device__ static __forceinline__ double term_qw(term_t const &t) {
         const unsigned long long bits = ((unsigned long long)t.y << 32) | t.x;
@@ -664,11 +716,34 @@ struct oc_solver {
             const job_t job = scalar_load(prm.jobs + t);
             [[maybe_unused]] int no1 = 0, no2 = 0;     // QUOT: nodes of the full graphs
             graph_header_t h1 = load_header(headers + job.i, no1), h2 = load_header(headers + job.j, no2);
+            // QSET: the output addresses of the epilogue share this round trip
+            [[maybe_unused]] unsigned out_i = 0, out_j = 0, out_t = 0;
+            if constexpr (QSET) {
+                out_i = scalar_load(prm.starts + job.i);
+                out_j = scalar_load(prm.starts + job.j);
+                out_t = scalar_load(prm.order + t);
+            }
+            // LANE_TABS: lane l of rows 0..2 (of 16 lanes) takes hist[l % 16]
+            // of either graph of the job -- in flight with the staging loads,
+            // first used behind them -- and its word of the rectangle table;
+            // row 3 takes hist[15], a zero (no graph of these kernels has a
+            // node of more than DMAX neighbours)
+            [[maybe_unused]] int hl_i = 0, hl_j = 0;
+            [[maybe_unused]] int rect_a1 = 0, rect_a2 = 0;
+            [[maybe_unused]] unsigned rect_cell = 0;
+            if constexpr (LANE_TABS) {
+                const int hk = lane < 48 ? lane & 15 : 15;
+                hl_i = (int)headers[job.i].hist[hk];
+                hl_j = (int)headers[job.j].hist[hk];
+                rect_a1 = RECT.a1[lane];
+                rect_a2 = RECT.a2[lane];
+                rect_cell = RECT.cell[lane];
+            }
+            [[maybe_unused]] bool flip = false;
             if constexpr (ORIENT) {
                 // the job's second graph plays graph 1 if it has a node of more
                 // than GV neighbours (wave-uniform: the headers are scalars,
                 // and both are loaded either way)
-                bool flip = false;
 #pragma unroll
                 for (int d = GV + 1; d <= DMAX; ++d) flip |= h2.hist[d] != 0;
                 if (flip) {
@@ -682,9 +757,18 @@ struct oc_solver {
             }
             const int n1 = h1.n_node, n2 = h2.n_node, N = n1 * n2;
             const int ldp = n2 | 1;            // odd row stride of p: banks spread
-            const real q = prm.q, q0 = prm.q0;
-            const real inv1q2 = real(1) / ((real(1) - q) * (real(1) - q));
-            const real bscale = q * q / (q0 * q0);
+            [[maybe_unused]] const real q = prm.q, q0 = prm.q0;
+            real inv1q2, bscale;
+            if constexpr (EVSC) {
+                struct scalars_t { real inv1q2, bscale; };
+                const scalars_t sc = scalar_load(reinterpret_cast<scalars_t const *>(
+                    prm.tables + prm.n_vclass * prm.n_vclass + prm.n_eclass * prm.n_eclass));
+                inv1q2 = sc.inv1q2;
+                bscale = sc.bscale;
+            } else {
+                inv1q2 =real(1) / ((real(1) - q) * (real(1) - q));
+                bscale = q * q / (q0 * q0);
+            }
             // label-class section in front of each image (_devicegraph.class_bytes):
             // u8 node classes [pad4(n)], u8 edge classes [pad4(nnz)], 16-aligned
             const unsigned nzpad1 = ((unsigned)n1 + 3u) & ~3u, nzpad2 = ((unsigned)n2 + 3u) & ~3u;
@@ -713,8 +797,29 @@ struct oc_solver {
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
                         const unsigned w = base + k * T + tid;
-                        v1[k] = w < w1 ? s1[w] : v4{0u, 0u, 0u, 0u};
-                        v2[k] = w < w2 ? s2[w] : v4{0u, 0u, 0u, 0u};
+                        if constexpr (QSET) {
+                            // no guard on the loads, only on the stores below.
+                            // A chunk that begins past an image re-reads the
+                            // image's last chunk (wave-uniform clamp), so a
+                            // lane reads less than T * 16 bytes behind an
+                            // image: the next blob of the arena, or the slack
+                            // behind the last one (HIPBackend._arena).
+                            const unsigned c = base + k * T;
+                            const unsigned c1 = c < w1 ? c : w1 ? (w1 - 1u) / T * T : 0u;
+                            const unsigned c2 = c < w2 ? c : w2 ? (w2 - 1u) / T * T : 0u;
+                            // (32-bit byte offsets from the uniform bases; the
+                            // pins keep a load from sinking under the guard
+                            // of its store, where it would wait alone)
+                            v1[k] = *reinterpret_cast<const v4 *>(reinterpret_cast<const char *>(s1) + (c1 + (unsigned)tid) * 16u);
+                            v2[k] = *reinterpret_cast<const v4 *>(reinterpret_cast<const char *>(s2) + (c2 + (unsigned)tid) * 16u);
+                        } else {
+                            v1[k] = w < w1 ? s1[w] : v4{0u, 0u, 0u, 0u};
+                            v2[k] = w < w2 ? s2[w] : v4{0u, 0u, 0u, 0u};
+                        }
+                    }
+                    if constexpr (QSET) {
+#pragma unroll
+                        for (int k = 0; k < K; ++k) asm volatile("" : "+v"(v1[k]), "+v"(v2[k]));
                     }
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
@@ -826,7 +931,44 @@ struct oc_solver {
             GD_OC_STAMP(1);
             // ---- degree histograms -> offsets of the degree-pair rectangles ---
             // (every wave computes the same wave-uniform numbers)
-            if constexpr (!FLY) {
+            if constexpr (LANE_TABS) {
+                // Per lane.  `cnt` holds the histogram of graph 1 in row 0
+                // (lanes 0..15), of graph 2 in rows 1 and 2, zeros in row 3
+                // and above DMAX (the host gives these kernels no graph of a
+                // larger degree).  Lane 32 - NCP + K owns the K-th rectangle
+                // of ORD: it fetches its two counts across the lanes, and
+                // the exclusive prefix sum of the products over the lanes is
+                // the rectangle's offset, scattered to its place d1 * NC + d2.
+                // (The other lanes multiply zeros and write the zeros that
+                // the lane writes left in the other cells: rectangle_lanes.)
+                static_assert(NCP > 16 && NCP <= 32, "rectangles in rows 0 and 1");
+
+                const int cnt = ((lane < 16) != flip) ? hl_i : hl_j;
+                const int c1 = __builtin_amdgcn_ds_bpermute(rect_a1, cnt);
+                const int c2 = __builtin_amdgcn_ds_bpermute(rect_a2, cnt);
+                const int size = (int)__umul24((unsigned)c1, (unsigned)c2);
+                int off = size;
+                off += __builtin_amdgcn_update_dpp(0, off, 0x111, 0xF, 0xF, true);   // row_shr:1
+                off += __builtin_amdgcn_update_dpp(0, off, 0x112, 0xF, 0xF, true);
+                off += __builtin_amdgcn_update_dpp(0, off, 0x114, 0xF, 0xF, true);
+                off += __builtin_amdgcn_update_dpp(0, off, 0x118, 0xF, 0xF, true);
+                // (across the rows as in wave.h: one instruction each, the
+                // builtin with a row mask is a move, a zero and an addition)
+                if constexpr (NCP > 16) asm("s_nop 1\n\tv_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa" : "+v"(off));
+                *reinterpret_cast<int *>(reinterpret_cast<char *>(lds.tab_off) + rect_cell) = off - size;
+                // class tables: the first node of class c comes after the
+                // nodes of the classes above it (descending degrees), an
+                // exclusive suffix sum of the counts within the row -- graph
+                // 1's starts in row 0, graph 2's in row 2; row 1 keeps graph
+                // 2's counts
+                int start = __builtin_amdgcn_update_dpp(0, cnt, 0x101, 0xF, 0xF, true);   // row_shl:1
+                if constexpr (NC > 2) start += __builtin_amdgcn_update_dpp(0, start, 0x101, 0xF, 0xF, true);
+                if constexpr (NC > 3) start += __builtin_amdgcn_update_dpp(0, start, 0x102, 0xF, 0xF, true);
+                if constexpr (NC > 5) start += __builtin_amdgcn_update_dpp(0, start, 0x104, 0xF, 0xF, true);
+                static_assert(NC <= 9, "the steps above sum up to eight classes");
+                const int vcls = __builtin_amdgcn_update_dpp(start, cnt, 0xE4, 0x2, 0xF, false);
+                lds.tab_cls[lane] = vcls;
+            } else if constexpr (!FLY) {
                 // (the packer leaves the degree histogram of every graph in its
                 // header: scalar registers, no ballots over the row pointers)
                 int cnt1[NC], cnt2[NC];
@@ -1035,6 +1177,18 @@ struct oc_solver {
                     // than the 12 it has -- it keeps the loads of the loop)
                     constexpr bool GPRE = QUOT && TAB && G0 > 0 &&
                         !(sizeof(real) == 8 && G0 == 16 && S == 20 && R == 2);
+                    // GWSEL: the weights of the half-terms beyond the degrees
+                    // are zeroed here, GU + GV selects, and a slot is the two
+                    // products alone -- an invalid one an exact zero times a
+                    // finite table value -- instead of a select per slot
+                    constexpr bool GWSEL = RECS && GPRE;
+                    if constexpr (GWSEL) {
+#pragma unroll
+                        for (int k = 0; k < GU; ++k) {
+                            gw1[k] = grid.u[k] ? gw1[k] : real(0);
+                            if (k < GV) gw2[k] = grid.v[k] ? gw2[k] : real(0);
+                        }
+                    }
                     [[maybe_unused]] real gtab[GPRE ? G0 : 1];
                     if constexpr (GPRE) {
 #pragma unroll
@@ -1113,6 +1267,8 @@ struct oc_solver {
                             // lane addresses a real element, as in the grid)
                             val[s] = e;
                             wok[s % SETUP_CHUNK] = ok;
+                        } else if (GWSEL && s < G0) {
+                            val[s] = e;
                         } else {
                             val[s] = ok ? e : real(0);
                         }
@@ -1434,8 +1590,15 @@ struct oc_solver {
                 if constexpr (FLY) rowid[k] = ok ? rm : ~0u;
                 const int i1 = (int)(rm >> 16), i2 = (int)(rm & 0xFFFFu);
                 const node_t v1 = at32(g1.node, (unsigned)i1), v2 = at32(g2.node, (unsigned)i2);
-                const real dx = real(at32(g1.degree, (unsigned)i1)) *
-                                real(at32(g2.degree, (unsigned)i2)) * inv1q2;
+                real dd = real(at32(g1.degree, (unsigned)i1)) * real(at32(g2.degree, (unsigned)i2));
+                // (EVSC, double: with the factor in scalar registers fast-math
+                // takes it to one of the degrees first, (inv d1) d2 -- an ulp
+                // away from the (d1 d2) inv of the in-kernel form; the pin
+                // keeps the product of the degrees whole, and K its bits.
+                // The float kernels keep theirs without it, and lose them
+                // with it.)
+                if constexpr (EVSC && sizeof(real) == 8) asm("" : "+v"(dd));
+                const real dx = dd * inv1q2;
                 const real vx = kappa_v(i1, i2, v1, v2);
                 // (double: two reciprocals of 6 instructions instead of the two
                 // divisions of 11 the compiler expands -- cg_ratio above)
@@ -1818,7 +1981,7 @@ struct oc_solver {
             if constexpr (SEQ) it = (it + 1u) / 2u;   // (iterations per system)
             GD_MARK(epilogue);
             GD_OC_STAMP(4);
-            if (prm.iters != nullptr && tid == 0) prm.iters[prm.order[t]] = it;
+            if (prm.iters != nullptr && tid == 0) prm.iters[QSET ? out_t : prm.order[t]] = it;
             if constexpr (LEAN) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) {
@@ -1831,7 +1994,7 @@ struct oc_solver {
 
             // ---- output ------------------------------------------------------
             const unsigned flags = prm.flags;
-            const unsigned I1 = prm.starts[job.i], I2 = prm.starts[job.j];
+            const unsigned I1 = QSET ? out_i : prm.starts[job.i], I2 = QSET ? out_j : prm.starts[job.j];
             const bool mirror = (flags & F_SYMMETRIC) && job.i != job.j;
             real ksum = 0;
             if constexpr (!KEEP_X) {
@@ -2044,7 +2207,7 @@ struct oc_solver {
                 ksum = reduce::sum(ksum, red0);
                 if (tid == 0) {
                     if (flags & F_PACKED) {
-                        prm.gramian[prm.order[t]] = ksum;
+                        prm.gramian[QSET ? out_t : prm.order[t]] = ksum;
                     } else if (flags & F_DIAGONAL) {
                         prm.gramian[I1] = ksum;
                     } else {

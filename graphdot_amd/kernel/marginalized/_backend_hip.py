@@ -184,6 +184,11 @@ WPB1 = 1
 TABLE_LDS_LIMIT = 8 * 1024
 #: class pairs (node + edge) up to which the global tables are used
 GLOBAL_TABLE_LIMIT = 1 << 16
+#: bytes allocated behind the last blob of an arena on the device: the
+#: one-wave quotient solvers stage an image with unguarded 16-byte loads, two
+#: per lane and trip (mgk_oc.h QSET); the host arena and its bytes stay as
+#: they are
+ARENA_SLACK = 2 * 64 * 16
 
 
 def _real_name(real):
@@ -749,7 +754,9 @@ class HIPBackend(Backend):
             self._arenas.move_to_end(key)
             return hit
         arena = self._host_arena(dgraphs, fields)
-        buf = runtime.DeviceBuffer(arena.nbytes)
+        # (slack behind the last blob: the staging loads of the one-wave
+        # quotient solvers carry no per-lane guard, mgk_oc.h QSET)
+        buf = runtime.DeviceBuffer(arena.nbytes + ARENA_SLACK)
         buf.upload(arena.relocated(buf.ptr))
         runtime.synchronize()
         self._arenas[key] = (arena, buf, list(dgraphs))
@@ -2457,7 +2464,8 @@ void ${name}(params_t prm) {
             planes = 1 + (len(node_kernel.gen_expr('x1', 'x2')[1]) +
                           len(edge_kernel.gen_expr('x1', 'x2')[1])
                           if C == 2 else 0)
-            n_tab = (c['nv']**2 + c['ne']**2) * planes
+            # (+ 2: the scalars of the evaluation, mgk_oc.h fill_tables)
+            n_tab = (c['nv']**2 + c['ne']**2) * planes + 2
             b_tables = self._buffer('tables', n_tab * rsize)
         b_hot = self._buffer('hotspot', 4 * n_out) if maximin else None
         plan.buffers = dict(jobs=lay.b_jobs, order=lay.b_order,
