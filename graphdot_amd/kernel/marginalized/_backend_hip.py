@@ -15,6 +15,7 @@ import re
 import uuid
 import zlib
 from collections import OrderedDict, namedtuple
+from typing import NamedTuple
 import numpy as np
 from ...codegen import Template
 from ...util import gcpause
@@ -371,6 +372,27 @@ class Partition(tuple):
     merge_map = {}
 
 
+class CallShape(NamedTuple):
+    """What a call is, as far as classification and code generation look:
+    made by `HIPBackend._call_shape` ("The host plan of a call")."""
+    C: int                    # right-hand sides: 2 = value + analytic gradient
+    nodal: bool = False
+    ngrad: bool = False       # finite-difference Jacobian in the launch
+    maximin: int = 0          # epilogue: 0 none, 1 maximin, 2 M3
+    quot: bool = False        # twin-leaf quotient images
+    tab_bytes: int = 0        # LDS tables of the two-stage solvers
+    gtab: bool = False        # global tables of the owner-computes solvers
+    oc_only: bool = False     # solver menu: owner-computes only
+    mfma: bool = False        # solver menu: the dense-tile MFMA solver
+    tab = property(lambda self: self.tab_bytes > 0)
+
+
+#: one record of `HIPBackend._host_plans`: images a call may run on and what
+#: the host decides for them; `layout` holds it all (`HIPBackend._layout`)
+HostPlan = namedtuple('HostPlan',
+                      'dgraphs edge_kernel fields shape arena part layout')
+
+
 class NotOwnerComputes(Exception):
     """Some pair of the call does not fit an owner-computes solver variant
     (raised when a feature only those solvers have was asked for)."""
@@ -378,12 +400,10 @@ class NotOwnerComputes(Exception):
 
 class Plan:
     """Everything resident on the device for one kernel evaluation."""
-    pass
 
 
 class Layout:
     """The hyperparameter-independent part of a Plan (HIPBackend._layout)."""
-    pass
 
 
 #: code objects loaded in this process, by JIT cache key (shared by backends)
@@ -843,11 +863,12 @@ struct ${name}_t : ${name}_theta_t {
                     pack.append(o.state)
         return pack
 
+    def _theta_dtype(self, obj):
+        dt = widen_theta(obj.dtype, self.real)
+        return dt if dt.itemsize else np.dtype(np.uint8)
+
     def _params_dtype(self, node_kernel, edge_kernel, p):
-        def theta(obj):
-            dt = widen_theta(obj.dtype, self.real)
-            return dt if dt.itemsize else np.dtype(np.uint8)
-        P = np.uintp
+        P, theta = np.uintp, self._theta_dtype
         return np.dtype([
             ('arena', P), ('jobs', P), ('order', P), ('starts', P),
             ('gramian', P), ('gradient', P), ('iters', P), ('scratch', P),
@@ -869,9 +890,7 @@ struct ${name}_t : ${name}_theta_t {
     def _params_fd_dtype(self, node_kernel, edge_kernel, p):
         """Kernel arguments of the nodal finite-difference gradient solver:
         graphdot::mgk::params_fd_t (mgk_oc.h)."""
-        def theta(obj):
-            dt = widen_theta(obj.dtype, self.real)
-            return dt if dt.itemsize else np.dtype(np.uint8)
+        theta = self._theta_dtype
         nv = len(node_kernel.gen_expr('x1', 'x2')[1])
         ne = len(edge_kernel.gen_expr('x1', 'x2')[1])
         return np.dtype([
@@ -1464,13 +1483,13 @@ void ${name}(params_t prm) {
         and a set of graphs has few distinct ones (about 150 among the 1000
         QM7-like molecules): large job lists are classified once per pair of
         graph classes and looked up."""
-        sel, out = self._classify_classes(ji, jj, dgraphs, C, tab_bytes, gtab,
-                                          oc_only, nodal=nodal, mfma=mfma)
+        sel, out = self._classify_classes(ji, jj, dgraphs, CallShape(
+            C, nodal=nodal, tab_bytes=tab_bytes, gtab=gtab, oc_only=oc_only,
+            mfma=mfma))
         out = out[:6]      # (the seventh, the larger node count, is _partition's)
         return out if sel is None else tuple(a[sel.sel] for a in out)
 
-    def _classify_classes(self, ji, jj, dgraphs, C, tab_bytes=0, gtab=False,
-                          oc_only=False, jobs=None, nodal=False, mfma=False):
+    def _classify_classes(self, ji, jj, dgraphs, shape, jobs=None):
         """(sel, per-class-pair results): job t has the results of class pair
         sel.sel[t] (`ClassPairs`: class-pair key per job, jobs per key); sel is
         None for short job lists (results are per job).  `jobs`: the job list
@@ -1481,8 +1500,7 @@ void ${name}(params_t prm) {
                 ji, jj = jobs['i'], jobs['j']
             ji = np.asarray(ji, dtype=np.int64)
             jj = np.asarray(jj, dtype=np.int64)
-            return None, self._classify_pairs(ji, jj, dgraphs, C, tab_bytes,
-                                              gtab, oc_only, nodal, mfma)
+            return None, self._classify_pairs(ji, jj, dgraphs, shape)
         # graphs of one degree histogram and image size are classified alike
         f = graph_features(dgraphs)
         if int(f['max_degree'].max()) < HIST_BINS - 1:
@@ -1518,8 +1536,8 @@ void ${name}(params_t prm) {
             pk = cid[ji] * np.int32(nc) + cid[jj]
             count = np.bincount(pk, minlength=nc * nc)
         upk = np.flatnonzero(count)
-        out = self._classify_pairs(rep[upk // nc], rep[upk % nc], dgraphs, C,
-                                   tab_bytes, gtab, oc_only, nodal, mfma)
+        out = self._classify_pairs(rep[upk // nc], rep[upk % nc], dgraphs,
+                                   shape)
         return ClassPairs(pk, upk, count, nc), out
 
     #: row batches the trip tables cover (static layouts have at most this many)
@@ -1550,8 +1568,10 @@ void ${name}(params_t prm) {
         tr = self.oc_trips(H[upk // nH], H[upk % nH], D, self.TRIP_BATCHES)
         return tr, row
 
-    def _classify_pairs(self, ji, jj, dgraphs, C, tab_bytes=0, gtab=False,
-                        oc_only=False, nodal=False, mfma=False):
+    def _classify_pairs(self, ji, jj, dgraphs, shape):
+        C, nodal, tab_bytes, gtab = shape.C, shape.nodal, shape.tab_bytes, \
+            shape.gtab
+        oc_only, mfma = shape.oc_only, shape.mfma
         f = graph_features(dgraphs)
         n_node, n_nz = f['n_node'], f['n_nz']
         deg_sorted = None      # (the two-stage variants' walk: made on demand)
@@ -1858,15 +1878,15 @@ void ${name}(params_t prm) {
         return all(isinstance(L['variant'], OCVariant) and L['variant'].S > 0
                    for L in launches)
 
-    def _partition(self, dgraphs, jobs, C, tab_bytes=0, gtab=False,
-                   oc_only=False, merge_map=None, nodal=False, mfma=False):
+    def _partition(self, dgraphs, jobs, shape, merge_map=None):
         """Host half of a layout: solver variant per job, launch order (by
         variant, then descending cost) and launch geometry.  No device."""
+        C, nodal, tab_bytes, gtab = shape.C, shape.nodal, shape.tab_bytes, \
+            shape.gtab
         jobs = np.ascontiguousarray(jobs)
         jobs_sorted = None             # (set by the native ordering)
         sel, (choice, cost, ntask, gbytes, NP, gbytes_oc, nmax) = \
-            self._classify_classes(None, None, dgraphs, C, tab_bytes, gtab,
-                                   oc_only, jobs=jobs, nodal=nodal, mfma=mfma)
+            self._classify_classes(None, None, dgraphs, shape, jobs=jobs)
         # Launch order: by variant, then descending cost, then job index.
         # `choice` ... `gbytes_oc` are per class pair (or per job when sel is
         # None); the jobs are ordered by the rank of their class pair with one
@@ -1918,9 +1938,8 @@ void ${name}(params_t prm) {
                             applied[k0] = k2
                     applied[k] = k2
                     break
-        choice = self._fit_launches_into_lds(choice, C, NP, ntask, gbytes,
-                                             gbytes_oc, tab_bytes, oc_only,
-                                             nodal)
+        choice = self._fit_launches_into_lds(choice, shape, NP, ntask, gbytes,
+                                             gbytes_oc)
         rank_of = np.empty(len(choice), dtype=np.int64)
         by_rank = np.lexsort((-cost, choice))
         # class pairs of equal (variant, cost) share a rank: their jobs stay
@@ -1957,22 +1976,14 @@ void ${name}(params_t prm) {
                 # one workgroup per pair, CG vectors + U in global scratch
                 # (rows N <= padded rows NP)
                 per_wg = int(((3 * NP[idx] + ntask[idx]) * C).max())
-                launches.append(dict(
-                    variant=v, k=k, offset=cursor, ucap=per_wg, gcap=0,
-                    dynamic_lds=0, count=count, grid=None,
-                    threads=GENERAL_THREADS, per_wg=per_wg))
-                cursor += count
-                continue
-            if v == MFMA:
+                geo = dict(ucap=per_wg, gcap=0, dynamic_lds=0, grid=None,
+                           threads=GENERAL_THREADS, per_wg=per_wg)
+            elif v == MFMA:
                 # one wave per pair; dynamic LDS: the two images
                 gcap = int(-(-gbytes[idx].max() // 16) * 16)
-                launches.append(dict(
-                    variant=v, k=k, offset=cursor, ucap=0, gcap=gcap,
-                    dynamic_lds=2 * gcap, count=count, grid=count,
-                    threads=64))
-                cursor += count
-                continue
-            if v == STREAM:
+                geo = dict(ucap=0, gcap=gcap, dynamic_lds=2 * gcap, grid=count,
+                           threads=64)
+            elif v == STREAM:
                 # one to 256 workgroups per pair; scratch [x | r | p | Ap |
                 # diag (| second solution)] (N <= NP reals each); LDS: image
                 # of B | staged rows of p | partial sums
@@ -1983,13 +1994,9 @@ void ${name}(params_t prm) {
                 # (a tuple: launch descriptions are compared as values)
                 costs = tuple(np.sort(np.repeat(cost[idx], members[idx])
                                       .astype(np.float64))[::-1].tolist())
-                launches.append(dict(
-                    variant=v, k=k, offset=cursor, ucap=per_wg, gcap=dyn,
-                    dynamic_lds=dyn, count=count, costs=costs,
-                    grid=None, threads=STREAM_THREADS, per_wg=per_wg))
-                cursor += count
-                continue
-            if isinstance(v, OCVariant):
+                geo = dict(ucap=per_wg, gcap=dyn, dynamic_lds=dyn, costs=costs,
+                           grid=None, threads=STREAM_THREADS, per_wg=per_wg)
+            elif isinstance(v, OCVariant):
                 # one pair per workgroup; dynamic LDS: p | row sums | row map
                 # | two images (mgk_oc.h)
                 pcap = int(-(-(NP[idx].max() + 1) // 4) * 4)
@@ -2013,48 +2020,46 @@ void ${name}(params_t prm) {
                         pcap += 4
                         dyn += extra + 4 * C * rsize
                         dense = True
-                launches.append(dict(
-                    variant=v, k=k, offset=cursor, ucap=pcap, gcap=gcap,
-                    dynamic_lds=dyn, count=count,
+                geo = dict(
+                    ucap=pcap, gcap=gcap, dynamic_lds=dyn,
                     grid=int(max(1, -(-count // self.jobs_per_unit))),
-                    threads=64 * v.W, tab=gtab, dense=dense))
-                cursor += count
-                continue
-            wpb = WPB1 if v.W == 1 else 1
-            threads = 64 * v.W * wpb
-            # Many small workgroups (jobs_per_unit pairs per wave, default
-            # one) rather than one persistent grid: the hardware dispatcher
-            # then balances the load whatever the achieved residency is, and
-            # a launch of few jobs (a rare variant, one rank's shard of a
-            # multi-GPU run) still covers the chip.  Measured: 1 pair per wave
-            # = 8 per wave + 1 % on 500 500 pairs, + 28 % on 61 000.
-            per_unit = self.jobs_per_unit
-            grid = int(max(1, -(-count // (wpb * per_unit))))
-            ucap = int(-(-ntask[idx].max() // 64) * 64) + 64   # + zero pad
-            gcap = int(-(-gbytes[idx].max() // 16) * 16)
-            dyn = (ucap * C * rsize + 2 * gcap) * wpb + tab_bytes
-            launches.append(dict(variant=v, k=k, offset=cursor, ucap=ucap,
-                                 gcap=gcap, dynamic_lds=dyn, count=count,
-                                 grid=grid, threads=threads))
+                    threads=64 * v.W, tab=gtab, dense=dense)
+            else:
+                wpb = WPB1 if v.W == 1 else 1
+                # Many small workgroups (jobs_per_unit pairs per wave, default
+                # one) rather than one persistent grid: the hardware
+                # dispatcher then balances the load whatever the achieved
+                # residency is, and a launch of few jobs (a rare variant, one
+                # rank's shard of a multi-GPU run) still covers the chip.
+                # Measured: 1 pair per wave = 8 per wave + 1 % on 500 500
+                # pairs, + 28 % on 61 000.
+                grid = int(max(1, -(-count // (wpb * self.jobs_per_unit))))
+                ucap = int(-(-ntask[idx].max() // 64) * 64) + 64  # + zero pad
+                gcap = int(-(-gbytes[idx].max() // 16) * 16)
+                dyn = (ucap * C * rsize + 2 * gcap) * wpb + tab_bytes
+                geo = dict(ucap=ucap, gcap=gcap, dynamic_lds=dyn, grid=grid,
+                           threads=64 * v.W * wpb)
+            launches.append(dict(variant=v, k=k, offset=cursor, count=count,
+                                 **geo))
             cursor += count
         out = Partition((jobs, used, order_all, launches))
         out.jobs_sorted, out.merge_map = jobs_sorted, applied
         return out
 
-    def _launch_lds(self, v, C, NP, ntask, gbytes, gbytes_oc, tab_bytes,
-                    nodal=False):
+    def _launch_lds(self, v, shape, NP, ntask, gbytes, gbytes_oc):
         """LDS of a workgroup -- static and dynamic, `lds_bytes` -- of ONE
         launch of variant `v` over the given class pairs (or jobs): the
         regions are sized for the largest vector and the largest image among
         them -- two maxima that need not belong to one pair."""
         if isinstance(v, OCVariant):
-            return int(self.lds_bytes(v, C, int(NP.max()),
-                                      int(gbytes_oc.max()), nodal=nodal))
-        return int(self.lds_bytes(v, C, int(ntask.max()), int(gbytes.max()),
-                                  tab_bytes))
+            return int(self.lds_bytes(v, shape.C, int(NP.max()),
+                                      int(gbytes_oc.max()),
+                                      nodal=shape.nodal))
+        return int(self.lds_bytes(v, shape.C, int(ntask.max()),
+                                  int(gbytes.max()), shape.tab_bytes))
 
-    def _fit_launches_into_lds(self, choice, C, NP, ntask, gbytes, gbytes_oc,
-                               tab_bytes, oc_only, nodal=False):
+    def _fit_launches_into_lds(self, choice, shape, NP, ntask, gbytes,
+                               gbytes_oc):
         """Every pair was given a variant whose LDS regions hold IT; a launch
         sizes its regions for the largest vector and the largest graph image
         among its pairs, and the two can come from different pairs: the sum
@@ -2064,7 +2069,6 @@ void ${name}(params_t prm) {
         170 mixed graphs -- invalid launches, scripts/fuzz_parity.py seeds 23
         and 51.  Pairs that hold one of the two maxima of such a launch leave
         for the general solver until the launch fits."""
-        limit = LDS_LIMIT
         fallback = None
         for k in sorted(set(choice.tolist())):
             v = self.variants[k]
@@ -2073,11 +2077,11 @@ void ${name}(params_t prm) {
             while True:
                 idx = np.flatnonzero(choice == k)
                 if not len(idx) or self._launch_lds(
-                        v, C, NP[idx], ntask[idx], gbytes[idx],
-                        gbytes_oc[idx], tab_bytes, nodal) <= limit:
+                        v, shape, NP[idx], ntask[idx], gbytes[idx],
+                        gbytes_oc[idx]) <= LDS_LIMIT:
                     break
                 if fallback is None:
-                    if oc_only or GENERAL not in self.variants:
+                    if shape.oc_only or GENERAL not in self.variants:
                         raise NotOwnerComputes(
                             f'the pairs of variant {v} do not fit the LDS '
                             'of a compute unit together and the general '
@@ -2092,8 +2096,8 @@ void ${name}(params_t prm) {
                     out = idx[key == key.max()]
                     keep = np.setdiff1d(idx, out)
                     after = self._launch_lds(
-                        v, C, NP[keep], ntask[keep], gbytes[keep],
-                        gbytes_oc[keep], tab_bytes, nodal) if len(keep) else 0
+                        v, shape, NP[keep], ntask[keep], gbytes[keep],
+                        gbytes_oc[keep]) if len(keep) else 0
                     cand.append((after, len(out), out))
                 after, _, out = min(cand, key=lambda c: (c[0], c[1]))
                 choice = choice.copy()
@@ -2101,9 +2105,7 @@ void ${name}(params_t prm) {
         return choice
 
     @staticmethod
-    def _code_signature(node_kernel, edge_kernel, p, dgraphs, C, nodal,
-                        tab=False, gtab=False, ngrad=False, maximin=False,
-                        quot=False):
+    def _code_signature(node_kernel, edge_kernel, p, dgraphs, shape):
         """What the generated code depends on: the microkernel expressions
         and record types (not the hyperparameter values), the graphs' record
         types and the output mode.  (The dtypes themselves, not their
@@ -2111,19 +2113,19 @@ void ${name}(params_t prm) {
         return (node_kernel.gen_expr('x1', 'x2')[0], np.dtype(node_kernel.dtype),
                 edge_kernel.gen_expr('x1', 'x2')[0], np.dtype(edge_kernel.dtype),
                 p.gen_expr()[0], np.dtype(p.dtype), dgraphs[0].signature,
-                C, nodal, tab, gtab, ngrad, maximin, quot)
+                shape.C, shape.nodal, shape.tab, shape.gtab, shape.ngrad,
+                shape.maximin, shape.quot)
 
-    def _sources(self, used, node_kernel, edge_kernel, p, dgraphs, C, nodal,
-                 tab=False, gtab=False, ngrad=False, maximin=False,
-                 quot=False):
+    def _sources(self, used, node_kernel, edge_kernel, p, dgraphs, shape):
         """One translation unit per solver variant in use (+ the one of the
         table kernel, key 'tables', when the owner-computes solvers read
         global tables).  The node / edge / start-probability code is shared
         text; only the entry point differs."""
         # rendering is pure text work on hyperparameter-independent inputs:
         # memoised on the generated expressions and the record types
-        sig = self._code_signature(node_kernel, edge_kernel, p, dgraphs, C,
-                                   nodal, tab, gtab, ngrad, maximin, quot)
+        sig = self._code_signature(node_kernel, edge_kernel, p, dgraphs,
+                                   shape)
+        C, gtab, ngrad = shape.C, shape.gtab, shape.ngrad
         out = {}
         todo = [(k, self.variants[k]) for k in used]
         if gtab and any(isinstance(v, OCVariant) for _, v in todo):
@@ -2139,12 +2141,13 @@ void ${name}(params_t prm) {
             if key not in self._source_cache:
                 self._source_cache[key] = self.render_source(
                     node_kernel, edge_kernel, p, dgraphs[0].node_t,
-                    dgraphs[0].edge_t, [v], C, nodal,
-                    tab=gtab if isinstance(v, OCVariant)
-                    else (tab and v not in (GENERAL, TABLES, STREAM, MFMA)),
+                    dgraphs[0].edge_t, [v], C, shape.nodal,
+                    tab=gtab if isinstance(v, OCVariant) else (
+                        shape.tab and v not in (GENERAL, TABLES, STREAM,
+                                                MFMA)),
                     weighted=dgraphs[0].weighted, ngrad=ngrad,
-                    maximin=maximin if isinstance(v, OCVariant) else False,
-                    quot=quot)
+                    maximin=shape.maximin if isinstance(v, OCVariant)
+                    else False, quot=shape.quot)
             out[k] = self._source_cache[key]
         return out
 
@@ -2156,53 +2159,89 @@ void ${name}(params_t prm) {
                 and os.environ.get('GD_MFMA', '1') != '0'
                 and getattr(edge_kernel, 'name', None) == 'Constant')
 
-    def _frontend(self, graphs, node_kernel, edge_kernel, p, jobs, traits,
-                  timer=None):
-        """Host-only half of `prepare` (used by `precompile`): pack graphs,
-        partition the jobs and render one translation unit per solver variant
-        in use."""
+    # -- the host plan of a call ("The host plan of a call") ---------
+    def _call_shape(self, arena, traits, C, edge_kernel_in, ngrad=False,
+                    maximin=0, quot=False):
+        """The `CallShape` of a call on the images of `arena`: every rule on
+        tables and solver menu, here and nowhere else.  `edge_kernel_in`: as
+        the caller gave it.  `arena` None: tables undecided (0, False) -- the
+        layout cache is keyed before an arena exists."""
+        # (owner-computes solvers that evaluate the microkernels directly)
+        direct = bool(ngrad or maximin)
+        return CallShape(
+            C=C, nodal=not quot and traits.nodal is not False, ngrad=ngrad,
+            maximin=maximin, quot=quot,
+            tab_bytes=0 if arena is None or direct
+            else self._table_bytes(arena),
+            gtab=bool(arena is not None and self._global_tables(arena)
+                      and not ngrad),
+            oc_only=direct,
+            mfma=not quot and self._label_blind(edge_kernel_in))
+
+    def _host_plans(self, graphs, node_kernel, edge_kernel, jobs, traits,
+                    ngrad=False, maximin=0, merge_map=None, quotient=None,
+                    layout_of=None, timer=None):
+        """The `HostPlan`s of a call, best first and made lazily: the
+        twin-leaf quotient images, when `_quotient_graphs` offers them and
+        `_quotient_launches` takes their partition, then the full images.
+        `precompile` and `prepare` take the first, `measured_shard_plan` all.
+        `merge_map` / `quotient`: as for `prepare`; a shard runs on the
+        quotient only where its whole list does.  `layout_of(dgraphs, fields,
+        shape without tables, merging, make)`: the device path (`_layout`):
+        its uploaded arena, and a cache hit makes neither arena nor partition."""
+        tic = timer.tic if timer else (lambda *_: None)
+        toc = timer.toc if timer else (lambda *_: None)
         edge_kernel_in = edge_kernel
         dgraphs, edge_kernel, C, fields = self._graphs_and_kernels(
-            graphs, node_kernel, edge_kernel, traits, timer)
-        jobs_in = jobs
-        for quot in (True, False):
-            dgs = self._quotient_graphs(graphs, dgraphs, traits, C) \
-                if quot else dgraphs
+            graphs, node_kernel, edge_kernel, traits, timer, ngrad)
+        qgraphs = self._quotient_graphs(graphs, dgraphs, traits, C, ngrad,
+                                        maximin) \
+            if merge_map is None or quotient is not None else None
+        for dgs, quot, mm in ((qgraphs, True, quotient),
+                              (dgraphs, False, merge_map)):
             if dgs is None:
                 continue
-            arena = self._host_arena(dgs, fields)
-            tab_bytes = self._table_bytes(arena)
-            gtab = self._global_tables(arena)
-            jobs, used, order_all, launches = self._partition(
-                dgs, jobs_in, C, tab_bytes, gtab,
-                nodal=traits.nodal is not False,
-                mfma=self._label_blind(edge_kernel_in) and not quot)
-            if not quot or self._quotient_launches(launches):
-                break
-        dgraphs = dgs
-        sources = self._sources(used, node_kernel, edge_kernel, p, dgraphs, C,
-                                traits.nodal is not False, tab_bytes > 0,
-                                gtab, quot=quot)
-        return dgraphs, edge_kernel, jobs, C, used, order_all, launches, \
-            sources
+
+            def make():        # (closes over dgs, quot, mm: call it at once)
+                lay = Layout()
+                tic('  arena and label classes')
+                if layout_of is None:
+                    lay.arena = self._host_arena(dgs, fields)
+                else:
+                    lay.arena, lay.arena_buf, _ = self._arena(dgs, fields)
+                toc('  arena and label classes')
+                lay.shape = self._call_shape(
+                    lay.arena, traits, C, edge_kernel_in, ngrad, maximin, quot)
+                tic('  solver variants and launch order')
+                lay.part = self._partition(dgs, jobs, lay.shape, mm)
+                toc('  solver variants and launch order')
+                return lay
+            lay = make() if layout_of is None else layout_of(
+                dgs, fields, self._call_shape(None, traits, C, edge_kernel_in,
+                                              ngrad, maximin, quot),
+                mm, make)
+            if not quot or self._quotient_launches(lay.part[3]):
+                yield HostPlan(dgs, edge_kernel, fields, lay.shape, lay.arena,
+                               lay.part, lay)
 
     def precompile(self, graphs, node_kernel, edge_kernel, p, jobs, traits):
         """Compile (into the on-disk JIT cache) every code object that
         `prepare` would need for this call.  Needs hipcc but no device."""
-        *_, sources = self._frontend(graphs, node_kernel, edge_kernel, p,
-                                     jobs, traits)
+        host = next(self._host_plans(graphs, node_kernel, edge_kernel, jobs,
+                                     traits))
+        sources = self._sources(host.part[1], node_kernel, host.edge_kernel,
+                                p, host.dgraphs, host.shape)
         return jit.compile_many(list(sources.values()), self.hipcc_extra)
 
-    def _layout(self, dgraphs, jobs, starts, C, fields=(None, None),
-                timer=None, ngrad=False, maximin=False, merge_map=None,
-                nodal=False, mfma=False):
+    def _layout(self, jobs, starts, timer, dgraphs, fields, shape, merge_map,
+                make):
         """Everything of a plan that depends only on WHICH pairs of WHICH
-        graphs are evaluated: variant per job, launch order and geometry, and
-        the device copies of the job list, the order and `starts`.  Cached
-        (LRU) on the identity of the packed graphs and a checksum of the job
-        list, so that repeated evaluations with new hyperparameters -- the
-        training loop of a Gaussian process -- skip the host-side work and
-        the uploads."""
+        graphs are evaluated: variant per job, launch order and geometry
+        (`make`: `_host_plans`), and the device copies of the job list, the
+        order and `starts`.  Cached (LRU) on the identity of the packed
+        graphs and a checksum of the job list, so that repeated evaluations
+        with new hyperparameters -- the training loop of a Gaussian process
+        -- skip the host-side work and the uploads."""
         jobs = np.ascontiguousarray(jobs)
         starts = np.ascontiguousarray(starts, dtype=np.uint32)
         # a read-only job list is recognised by identity (the kernel object
@@ -2210,8 +2249,9 @@ void ${name}(params_t prm) {
         jobs_id = ('id', id(jobs)) if not jobs.flags.writeable else \
             ('crc', zlib.crc32(jobs.view(np.uint8)))
         key = (_ids(dgraphs), len(jobs), jobs_id,
-               zlib.crc32(starts.view(np.uint8)), C, fields, self.tables,
-               ngrad, maximin, bool(nodal), bool(mfma),
+               zlib.crc32(starts.view(np.uint8)), shape.C, fields,
+               self.tables, shape.ngrad, shape.maximin, shape.nodal,
+               shape.mfma,
                None if merge_map is None else tuple(sorted(merge_map.items())))
         hit = self._layouts.get(key)
         if hit is not None:
@@ -2220,23 +2260,10 @@ void ${name}(params_t prm) {
         tic = timer.tic if timer else (lambda *_: None)
         toc = timer.toc if timer else (lambda *_: None)
         tic('calculating launch configuration')
-        lay = Layout()
-        lay.dgraphs = list(dgraphs)          # keeps the ids in `key` alive
-        lay.jobs_host = jobs
-        tic('  arena and label classes')
-        lay.arena, lay.arena_buf, _ = self._arena(dgraphs, fields)
-        toc('  arena and label classes')
-        lay.tab_bytes = self._table_bytes(lay.arena)
-        # (the nodal-gradient solvers evaluate the microkernels directly)
-        lay.gtab = self._global_tables(lay.arena) and not ngrad
-        if ngrad or maximin:
-            lay.tab_bytes = 0
-        tic('  solver variants and launch order')
-        part = self._partition(dgraphs, jobs, C, lay.tab_bytes, lay.gtab,
-                               oc_only=ngrad or maximin, merge_map=merge_map,
-                               nodal=nodal, mfma=mfma)
-        jobs, lay.used, lay.order_host, lay.launches = part
-        toc('  solver variants and launch order')
+        lay = make()
+        lay.dgraphs, lay.jobs_host = list(dgraphs), jobs   # (keeps ids alive)
+        lay.tab_bytes, lay.gtab = lay.shape.tab_bytes, lay.shape.gtab
+        jobs, lay.used, lay.order_host, lay.launches = part = lay.part
         tic('  job list to the device')
         lay.n_jobs = len(jobs)
         lay.b_jobs = runtime.DeviceBuffer(max(jobs.nbytes, 8))
@@ -2245,6 +2272,7 @@ void ${name}(params_t prm) {
         # jobs travel in launch order: the kernel reads jobs[t] directly
         sorted_jobs = part.jobs_sorted if part.jobs_sorted is not None \
             else np.ascontiguousarray(jobs[lay.order_host])
+        part.jobs_sorted = None              # (only the device keeps them)
         lay.b_jobs.upload(sorted_jobs.view(np.uint32))
         lay.b_order.upload(lay.order_host)
         lay.b_starts.upload(starts)
@@ -2257,6 +2285,190 @@ void ${name}(params_t prm) {
             self._layouts.popitem(last=False)    # freed with its last plan
         toc('calculating launch configuration')
         return lay
+
+    def _modules_of(self, host, node_kernel, p, timer=None):
+        """(module per solver variant in use, dtype of the argument block):
+        a repeated call -- same code -- renders, hashes and looks up nothing."""
+        tic = timer.tic if timer else (lambda *_: None)
+        toc = timer.toc if timer else (lambda *_: None)
+        tic('code generation')
+        used, edge_kernel = host.part[1], host.edge_kernel
+        mkey = (self._code_signature(node_kernel, edge_kernel, p,
+                                     host.dgraphs, host.shape), tuple(used),
+                tuple(self.hipcc_extra), self.tables,
+                None if self.occupancy is None
+                else tuple(sorted(self.occupancy.items())))
+        hit = self._module_sets.get(mkey)
+        if hit is not None:
+            toc('code generation')
+            return hit
+        sources = self._sources(used, node_kernel, edge_kernel, p,
+                                host.dgraphs, host.shape)
+        toc('code generation')
+        tic('JIT')
+        missing = [s for s in sources.values()
+                   if jit.cache_key(s, self.hipcc_extra) not in self._modules]
+        if len(missing) > 1:
+            jit.compile_many(missing, self.hipcc_extra)
+        modules = {k: self._module(s) for k, s in sources.items()}
+        toc('JIT')
+        hit = self._module_sets[mkey] = (
+            modules, self._params_dtype(node_kernel, edge_kernel, p))
+        return hit
+
+    @staticmethod
+    def _flag_word(traits, packed, maximin):
+        return sum(flag for flag, on in (
+            (F_NODAL, traits.nodal is True or traits.nodal == 'block'),
+            (F_BLOCK, traits.nodal == 'block'),
+            (F_DIAGONAL, traits.diagonal), (F_SYMMETRIC, traits.symmetric),
+            (F_LMIN1, traits.lmin == 1), (F_PACKED, packed),
+            (F_REFCOMPAT, maximin and maximin.get('reference_compat')),
+        ) if on)
+
+    def _launch_geometry(self, L):
+        """Grid and global scratch of the launches whose geometry follows
+        the chip: the streamed solver (cooperative) and the general solver."""
+        rsize = np.dtype(self.real).itemsize
+        if L['variant'] == STREAM:
+            # few pairs: several workgroups per pair, a cooperative
+            # launch (mgk_stream.h).  M = what the chip holds at once over
+            # the pairs; one workgroup per pair from half the chip up.
+            # (workgroups the chip holds at once, by this build's own
+            # arithmetic as well as by the runtime's: a grid beyond it
+            # would wait for workgroups that wait for it)
+            per_cu = max(1, min(
+                runtime.max_active_blocks(L['fn'], L['threads'],
+                                          L['dynamic_lds']),
+                LDS_LIMIT // (L['dynamic_lds'] + 1024),
+                2048 // L['threads']))
+            resident = self.props.compute_units * per_cu
+            parts = int(os.environ.get('GD_STREAM_PARTS', 0)) or \
+                stream_parts(L.get('costs'), L['count'], resident,
+                             2 * self.props.compute_units)
+            parts = max(1, min(parts, resident))
+            slots = int(min(L['count'], max(1, resident // parts)))
+            if parts == 1:
+                slots = int(min(L['count'], 2 * self.props.compute_units))
+            L['parts'], L['cooperative'] = parts, parts > 1
+            L['grid'] = slots * parts
+            L['scratch_bytes'] = slots * L['per_wg'] * rsize
+            L['sync_bytes'] = slots * 4 * (
+                16 + 2 * parts * 4 * (rsize // 4)) if parts > 1 else 0
+        elif L['variant'] == GENERAL:
+            L['grid'] = int(min(L['count'], 2 * self.props.compute_units))
+            L['scratch_bytes'] = L['grid'] * L['per_wg'] * rsize
+
+    @staticmethod
+    def _stream_hint(shape, launches, ftol):
+        # Streams the launches are dealt onto (LaunchSet): three by default
+        # (short launches fill the tails of long ones: +4-6 % over one, the
+        # dense molecular set +10 % over two), TWO for the double value plans
+        # of one-wave static layouts -- latency-bound kernels at two or three
+        # waves per SIMD whose dominant launch loses more residency to a
+        # third concurrent grid than its tail gains: 168.4-168.6 against
+        # 166.1-166.3 M pairs/s on the headline, alternating on one box
+        # (profiles/sessions.md r5_session29; float: equal; double value +
+        # gradient: three, 64.5 against 63.7 M; the same plans run to
+        # convergence, ftol 1e-13 and 26 iterations instead of 17: three, 126.6
+        # against 125.7 M, r5_session36 -- hence the tolerance in the rule).
+        # Round 6: the float value plans too -- equal on the full matrix, and on
+        # a rank's share of it (354 graphs, five launches) 0.342 against 0.373 ms
+        # per step (double: 0.447 against 0.455; one stream: 0.513 / 0.392;
+        # scripts/fixed_cost_experiment.sh, profiles/r06_fixed_cost.log).
+        return 2 if (
+            shape.C == 1 and not shape.nodal and not shape.ngrad
+            and len(launches) > 2 and ftol >= 1e-10
+            and all(isinstance(L['variant'], OCVariant) and L['variant'].L
+                    for L in launches)) else None
+
+    def _call_buffers(self, plan, modules, node_kernel, edge_kernel):
+        """The per-call device buffers (outputs, scratch) of `plan`, from the
+        grow-only pool; its launches get their scratch offsets."""
+        lay, launches, C = plan.layout, plan.launches, plan.C
+        rsize = np.dtype(self.real).itemsize
+        b = dict(jobs=lay.b_jobs, order=lay.b_order, starts=lay.b_starts)
+        b['gramian'] = self._buffer('gramian', plan.n_out * rsize)
+        b['gradient'] = self._buffer('gradient', plan.n_grad * rsize) \
+            if plan.n_grad else None
+        b['iters'] = self._buffer('iters', 4 * lay.n_jobs) \
+            if self.record_iterations else None
+        # (launches run concurrently on several streams: every launch that
+        # keeps CG vectors in global memory gets a region of its own)
+        scratch_bytes = 0
+        for L in launches:
+            if L.get('scratch_bytes', 0):
+                L['scratch_offset'] = scratch_bytes
+                scratch_bytes += -(-L['scratch_bytes'] // 256) * 256
+        b['scratch'] = self._buffer('scratch', scratch_bytes) \
+            if scratch_bytes else None
+        sync_bytes = max([L.get('sync_bytes', 0) for L in launches] + [0])
+        # (a buffer of its OWN per plan: the kernels leave the barrier cells
+        # clean at THIS plan's slot stride -- a pooled buffer re-used by a
+        # plan of another M had its counters on leftover partial sums, and
+        # the second evaluation of a backend dead-locked in its first barrier)
+        b['sync'] = self._zeroed_buffer(sync_bytes) if sync_bytes else None
+        # global microkernel tables of this evaluation: values (and, for the
+        # gradient solvers, one plane per hyperparameter) per pair of classes
+        b['tables'] = None
+        if 'tables' in modules:
+            c = lay.arena.classes
+            planes = 1 + (len(node_kernel.gen_expr('x1', 'x2')[1]) +
+                          len(edge_kernel.gen_expr('x1', 'x2')[1])
+                          if C == 2 else 0)
+            # (+ 2: the scalars of the evaluation, mgk_oc.h fill_tables)
+            n_tab = (c['nv']**2 + c['ne']**2) * planes + 2
+            b['tables'] = self._buffer('tables', n_tab * rsize)
+        b['hotspot'] = self._buffer('hotspot', 4 * plan.n_out) \
+            if plan.maximin else None
+        return b
+
+    def _fd_block(self, node_kernel, edge_kernel, p, q, eps):
+        """The hyperparameter sets exp(log(theta) +- eps) of the central
+        differences (pack_state(diff_grid=True), _backend_cuda.py:230-245)."""
+        fd = np.zeros((), dtype=self._params_fd_dtype(
+            node_kernel, edge_kernel, p))
+        fd['q_plus'] = np.exp(np.log(q) + eps)
+        fd['q_minus'] = np.exp(np.log(q) - eps)
+        for which, kern in (('node', node_kernel), ('edge', edge_kernel)):
+            theta = np.array(list(flatten(kern.theta)), dtype=float)
+            for j_, t_ in enumerate(theta):
+                fd[which + '_theta'][j_] = t_
+                for s_, delta in enumerate((eps, -eps)):
+                    k2 = copy.deepcopy(kern)
+                    lt = np.log(theta)
+                    lt[j_] += delta
+                    k2.theta = fold_like(np.exp(lt), k2.theta)
+                    _, val = pack_theta(k2, self.real)
+                    if val is not None:
+                        fd[which + '_diff'][2 * j_ + s_] = val
+        return fd
+
+    def _argument_blocks(self, plan, b, base, fd):
+        """`L['args']` of every launch of `plan`: `base` with the launch's
+        own fields, inside `fd` (`_fd_block`) when there is one."""
+        lay = plan.layout
+        for L in plan.launches:
+            a = base.copy()
+            a['order'] = lay.b_order.ptr + 4 * L['offset']
+            a['jobs'] = lay.b_jobs.ptr + 8 * L['offset']
+            a['g_capacity'] = L['gcap']
+            a['n_launch_jobs'] = L['count']
+            a['order_offset'] = L['offset']
+            a['u_capacity'] = L['ucap']
+            if L.get('scratch_bytes', 0):
+                a['scratch'] = b['scratch'].ptr + L['scratch_offset']
+            if L.get('parts', 1) > 1:
+                a['parts'], a['sync'] = L['parts'], b['sync'].ptr
+                plan.sync = (b['sync'], L['sync_bytes'])
+            if L.get('dense'):
+                a['flags'] |= F_DENSE
+            if fd is not None:
+                f_ = fd.copy()
+                f_['base'] = a
+                L['args'] = f_.tobytes()
+            else:
+                L['args'] = a.tobytes()
 
     def prepare(self, graphs, node_kernel, edge_kernel, p, q, eps, ftol, gtol,
                 jobs, starts, nX, nY, nJ, traits, timer=None, packed=False,
@@ -2279,276 +2491,81 @@ void ${name}(params_t prm) {
         (`_sharded.measured_shard_plan`: which images and which solver a pair
         runs on must not depend on the shard it falls into), or None: the
         full images."""
-        tic = timer.tic if timer else (lambda *_: None)
-        toc = timer.toc if timer else (lambda *_: None)
         runtime.ensure_device(self.device)
-        node_kernel_in, edge_kernel_in = node_kernel, edge_kernel
-        dgraphs, edge_kernel, C, fields = self._graphs_and_kernels(
-            graphs, node_kernel, edge_kernel, traits, timer, ngrad)
         # epilogue flavour: 0 none, 1 maximin, 2 M3 (mgk_oc.h MAXIMIN)
         flavour = 0 if maximin is None else (2 if maximin.get('m3') else 1)
-        # plain value calls: the twin-leaf quotient images, when every pair
-        # of them runs on a slot variant of the owner-computes solver
-        lay, quot = None, False
-        qgraphs = self._quotient_graphs(graphs, dgraphs, traits, C, ngrad,
-                                        flavour) \
-            if merge_map is None or quotient is not None else None
-        if qgraphs is not None:
-            lay = self._layout(qgraphs, jobs, starts, C, fields, timer,
-                               merge_map=quotient, nodal=False, mfma=False)
-            if self._quotient_launches(lay.launches):
-                dgraphs, quot = qgraphs, True
-            else:
-                lay = None
-        if lay is None:
-            lay = self._layout(dgraphs, jobs, starts, C, fields, timer, ngrad,
-                               flavour, merge_map,
-                               nodal=traits.nodal is not False,
-                               mfma=self._label_blind(edge_kernel_in))
-        tab = lay.tab_bytes > 0
-
-        tic('code generation')
-        nodal = traits.nodal is not False
-        # the loaded modules and the argument block of a (code signature, set
-        # of variants): a repeated call -- new hyperparameters, same code --
-        # renders, hashes and looks up nothing
-        mkey = (self._code_signature(node_kernel, edge_kernel, p, dgraphs, C,
-                                     nodal, tab, lay.gtab, ngrad,
-                                     flavour, quot), tuple(lay.used),
-                tuple(self.hipcc_extra), self.tables,
-                None if self.occupancy is None
-                else tuple(sorted(self.occupancy.items())))
-        hit = self._module_sets.get(mkey)
-        if hit is None:
-            sources = self._sources(lay.used, node_kernel, edge_kernel, p,
-                                    dgraphs, C, nodal, tab, lay.gtab, ngrad,
-                                    flavour, quot)
-            toc('code generation')
-            tic('JIT')
-            missing = [s for s in sources.values()
-                       if jit.cache_key(s, self.hipcc_extra)
-                       not in self._modules]
-            if len(missing) > 1:
-                jit.compile_many(missing, self.hipcc_extra)
-            modules = {k: self._module(s) for k, s in sources.items()}
-            toc('JIT')
-            hit = self._module_sets[mkey] = (
-                modules, self._params_dtype(node_kernel, edge_kernel, p))
-        else:
-            toc('code generation')
-        modules, pd = hit
+        # the first host plan: on the quotient images where they are taken
+        host = next(self._host_plans(
+            graphs, node_kernel, edge_kernel, jobs, traits, ngrad, flavour,
+            merge_map, quotient, timer=timer,
+            layout_of=lambda *a: self._layout(jobs, starts, timer, *a)))
+        lay, shape, dgraphs = host.layout, host.shape, host.dgraphs
+        edge_kernel, C = host.edge_kernel, shape.C
+        modules, pd = self._modules_of(host, node_kernel, p, timer)
 
         plan = Plan()
-        plan.layout = lay
+        plan.layout, plan.quotient, plan.packed = lay, shape.quot, packed
         plan.traits, plan.C, plan.n_jobs = traits, C, lay.n_jobs
-        plan.quotient = quot
         plan.nX, plan.nY, plan.nJ = int(nX), int(nY), int(nJ)
-        plan.packed = packed
         plan.keep = (lay.arena, lay.arena_buf, dgraphs)
         plan.order_host = lay.order_host
-        flags = 0
-        if traits.nodal is True or traits.nodal == 'block':
-            flags |= F_NODAL
-        if traits.nodal == 'block':
-            flags |= F_BLOCK
-        if traits.diagonal:
-            flags |= F_DIAGONAL
-        if traits.symmetric:
-            flags |= F_SYMMETRIC
-        if traits.lmin == 1:
-            flags |= F_LMIN1
-        if packed:
-            flags |= F_PACKED
-        if maximin and maximin.get('reference_compat'):
-            flags |= F_REFCOMPAT
-        rsize = np.dtype(self.real).itemsize
-        n_out = lay.n_jobs if packed else plan.nX * plan.nY
-        plan.n_out = n_out
-        plan.maximin = maximin is not None
-        plan.ngrad = ngrad
-        plan.n_grad = n_out * plan.nJ if (C == 2 or ngrad) else 0
+        plan.n_out = lay.n_jobs if packed else plan.nX * plan.nY
+        plan.maximin, plan.ngrad = maximin is not None, ngrad
+        plan.n_grad = plan.n_out * plan.nJ if (C == 2 or ngrad) else 0
 
-        launches = []
+        plan.launches = []
         for G in lay.launches:
             L = dict(G)
             L['module'] = modules[L['k']]
             L['tab'] = L.get('tab', False) \
                 if isinstance(L['variant'], OCVariant) \
-                else tab and L['variant'] not in (GENERAL, STREAM, MFMA)
-            L['fn'] = fn = L['module'].function(
-                self.kernel_name(L['variant'], C, nodal, L['tab'], ngrad,
-                                 flavour, quot))
-            if L['variant'] == STREAM:
-                # few pairs: several workgroups per pair, a cooperative
-                # launch (mgk_stream.h).  M = what the chip holds at once over
-                # the pairs; one workgroup per pair from half the chip up.
-                if L['dynamic_lds'] > 64 * 1024:
-                    runtime.set_max_dynamic_lds(fn, L['dynamic_lds'])
-                # (workgroups the chip holds at once, by this build's own
-                # arithmetic as well as by the runtime's: a grid beyond it
-                # would wait for workgroups that wait for it)
-                per_cu = max(1, min(
-                    runtime.max_active_blocks(fn, L['threads'],
-                                              L['dynamic_lds']),
-                    LDS_LIMIT // (L['dynamic_lds'] + 1024),
-                    2048 // L['threads']))
-                resident = self.props.compute_units * per_cu
-                parts = int(os.environ.get('GD_STREAM_PARTS', 0)) or \
-                    stream_parts(L.get('costs'), L['count'], resident,
-                                 2 * self.props.compute_units)
-                parts = max(1, min(parts, resident))
-                slots = int(min(L['count'], max(1, resident // parts)))
-                if parts == 1:
-                    slots = int(min(L['count'],
-                                    2 * self.props.compute_units))
-                L['parts'], L['cooperative'] = parts, parts > 1
-                L['grid'] = slots * parts
-                L['scratch_bytes'] = slots * L['per_wg'] * rsize
-                L['sync_bytes'] = slots * 4 * (
-                    16 + 2 * parts * 4 * (rsize // 4)) if parts > 1 else 0
-            elif L['variant'] == GENERAL:
-                L['grid'] = int(min(L['count'],
-                                    2 * self.props.compute_units))
-                L['scratch_bytes'] = L['grid'] * L['per_wg'] * rsize
+                else shape.tab and L['variant'] not in (GENERAL, STREAM, MFMA)
+            L['fn'] = L['module'].function(
+                self.kernel_name(L['variant'], C, shape.nodal, L['tab'],
+                                 ngrad, flavour, shape.quot))
             if L['dynamic_lds'] > 64 * 1024:
-                runtime.set_max_dynamic_lds(fn, L['dynamic_lds'])
-            launches.append(L)
-        plan.launches = launches
-        # Streams the launches are dealt onto (LaunchSet): three by default
-        # (short launches fill the tails of long ones: +4-6 % over one, the
-        # dense molecular set +10 % over two), TWO for the double value plans
-        # of one-wave static layouts -- latency-bound kernels at two or three
-        # waves per SIMD whose dominant launch loses more residency to a
-        # third concurrent grid than its tail gains: 168.4-168.6 against
-        # 166.1-166.3 M pairs/s on the headline, alternating on one box
-        # (profiles/sessions.md r5_session29; float: equal; double value +
-        # gradient: three, 64.5 against 63.7 M; the same plans run to
-        # convergence, ftol 1e-13 and 26 iterations instead of 17: three, 126.6
-        # against 125.7 M, r5_session36 -- hence the tolerance in the rule).
-        # Round 6: the float value plans too -- equal on the full matrix, and on
-        # a rank's share of it (354 graphs, five launches) 0.342 against 0.373 ms
-        # per step (double: 0.447 against 0.455; one stream: 0.513 / 0.392;
-        # scripts/fixed_cost_experiment.sh, profiles/r06_fixed_cost.log).
-        plan.stream_hint = 2 if (
-            C == 1 and not nodal
-            and not ngrad and len(launches) > 2 and ftol >= 1e-10
-            and all(isinstance(L['variant'], OCVariant) and L['variant'].L
-                    for L in launches)) else None
+                runtime.set_max_dynamic_lds(L['fn'], L['dynamic_lds'])
+            self._launch_geometry(L)
+            plan.launches.append(L)
+        plan.stream_hint = self._stream_hint(shape, plan.launches, ftol)
+        b = self._call_buffers(plan, modules, node_kernel, edge_kernel)
+        plan.buffers = {k: b[k] for k in (
+            'jobs', 'order', 'starts', 'gramian', 'gradient', 'iters',
+            'tables', 'hotspot')}
 
-        # per-call device buffers (outputs, scratch) from the grow-only pool
-        b_out = self._buffer('gramian', n_out * rsize)
-        b_grad = self._buffer('gradient', plan.n_grad * rsize) \
-            if plan.n_grad else None
-        b_iters = self._buffer('iters', 4 * lay.n_jobs) \
-            if self.record_iterations else None
-        # (launches run concurrently on several streams: every launch that
-        # keeps CG vectors in global memory gets a region of its own)
-        scratch_bytes = 0
-        for L in launches:
-            if L.get('scratch_bytes', 0):
-                L['scratch_offset'] = scratch_bytes
-                scratch_bytes += -(-L['scratch_bytes'] // 256) * 256
-        b_scratch = self._buffer('scratch', scratch_bytes) \
-            if scratch_bytes else None
-        sync_bytes = max([L.get('sync_bytes', 0) for L in launches] + [0])
-        # (a buffer of its OWN per plan: the kernels leave the barrier cells
-        # clean at THIS plan's slot stride -- a pooled buffer re-used by a
-        # plan of another M had its counters on leftover partial sums, and
-        # the second evaluation of a backend dead-locked in its first barrier)
-        b_sync = self._zeroed_buffer(sync_bytes) if sync_bytes else None
-        # global microkernel tables of this evaluation: values (and, for the
-        # gradient solvers, one plane per hyperparameter) per pair of classes
-        b_tables = None
-        if 'tables' in modules:
-            c = lay.arena.classes
-            planes = 1 + (len(node_kernel.gen_expr('x1', 'x2')[1]) +
-                          len(edge_kernel.gen_expr('x1', 'x2')[1])
-                          if C == 2 else 0)
-            # (+ 2: the scalars of the evaluation, mgk_oc.h fill_tables)
-            n_tab = (c['nv']**2 + c['ne']**2) * planes + 2
-            b_tables = self._buffer('tables', n_tab * rsize)
-        b_hot = self._buffer('hotspot', 4 * n_out) if maximin else None
-        plan.buffers = dict(jobs=lay.b_jobs, order=lay.b_order,
-                            starts=lay.b_starts, gramian=b_out,
-                            gradient=b_grad, iters=b_iters, tables=b_tables,
-                            hotspot=b_hot)
-
-        # kernel argument blocks
+        # the argument block all launches share
         base = np.zeros((), dtype=pd)
-        base['arena'] = lay.arena_buf.ptr
-        base['jobs'] = lay.b_jobs.ptr
-        base['starts'] = lay.b_starts.ptr
-        base['gramian'] = gramian_ptr if gramian_ptr else b_out.ptr
+        base['arena'], base['jobs'], base['starts'] = \
+            lay.arena_buf.ptr, lay.b_jobs.ptr, lay.b_starts.ptr
+        base['gramian'] = gramian_ptr if gramian_ptr else b['gramian'].ptr
         base['gradient'] = gradient_ptr if gradient_ptr else (
-            b_grad.ptr if b_grad is not None else 0)
-        base['iters'] = b_iters.ptr if b_iters is not None else 0
-        base['scratch'] = b_scratch.ptr if b_scratch is not None else 0
-        base['tables'] = b_tables.ptr if b_tables is not None else 0
+            b['gradient'].ptr if b['gradient'] is not None else 0)
+        for name in ('iters', 'scratch', 'tables'):
+            base[name] = b[name].ptr if b[name] is not None else 0
         if maximin:
             base['diag'], base['diag_grad'] = maximin['diag'], \
                 maximin.get('diag_grad', 0)
             base['node_starts'], base['diag_ld'] = maximin['node_starts'], \
                 maximin['ld']
-            base['hotspot'] = b_hot.ptr
+            base['hotspot'] = b['hotspot'].ptr
         base['nX'], base['nY'], base['nJ'] = plan.nX, plan.nY, plan.nJ
-        base['flags'] = flags
-        if tab or b_tables is not None:
+        base['flags'] = self._flag_word(traits, packed, maximin)
+        if shape.tab or b['tables'] is not None:
             c = lay.arena.classes
             base['n_vclass'], base['n_eclass'] = c['nv'], c['ne']
             base['vrep'], base['erep'] = c['vrep'], c['erep']
-        base['q'] = q
-        base['q0'] = q
+        base['q'] = base['q0'] = q
         base['eps'], base['ftol'], base['gtol'] = eps, ftol, gtol
         for field, obj in (('node_kernel', node_kernel),
                            ('edge_kernel', edge_kernel), ('p_start', p)):
             dt, val = pack_theta(obj, self.real)
             if val is not None:
                 base[field] = val
-        fd = None
-        if ngrad:
-            # perturbed hyperparameter sets exp(log(theta) +- eps) of the
-            # central differences (reference: pack_state(diff_grid=True),
-            # _backend_cuda.py:230-245)
-            fd = np.zeros((), dtype=self._params_fd_dtype(
-                node_kernel, edge_kernel, p))
-            fd['q_plus'] = np.exp(np.log(q) + eps)
-            fd['q_minus'] = np.exp(np.log(q) - eps)
-            for which, kern in (('node', node_kernel), ('edge', edge_kernel)):
-                theta = np.array(list(flatten(kern.theta)), dtype=float)
-                for j_, t_ in enumerate(theta):
-                    fd[which + '_theta'][j_] = t_
-                    for s_, delta in enumerate((eps, -eps)):
-                        k2 = copy.deepcopy(kern)
-                        lt = np.log(theta)
-                        lt[j_] += delta
-                        k2.theta = fold_like(np.exp(lt), k2.theta)
-                        _, val = pack_theta(k2, self.real)
-                        if val is not None:
-                            fd[which + '_diff'][2 * j_ + s_] = val
-        for L in launches:
-            a = base.copy()
-            a['order'] = lay.b_order.ptr + 4 * L['offset']
-            a['jobs'] = lay.b_jobs.ptr + 8 * L['offset']
-            a['g_capacity'] = L['gcap']
-            a['n_launch_jobs'] = L['count']
-            a['order_offset'] = L['offset']
-            a['u_capacity'] = L['ucap']
-            if L.get('scratch_bytes', 0):
-                a['scratch'] = b_scratch.ptr + L['scratch_offset']
-            if L.get('parts', 1) > 1:
-                a['parts'], a['sync'] = L['parts'], b_sync.ptr
-                plan.sync = (b_sync, L['sync_bytes'])
-            if L.get('dense'):
-                a['flags'] |= F_DENSE
-            if fd is not None:
-                f_ = fd.copy()
-                f_['base'] = a
-                L['args'] = f_.tobytes()
-            else:
-                L['args'] = a.tobytes()
+        self._argument_blocks(plan, b, base, self._fd_block(
+            node_kernel, edge_kernel, p, q, eps) if ngrad else None)
         # launches that every solver launch depends on: the table kernel
         plan.pre_launches = []
-        if b_tables is not None:
+        if b['tables'] is not None:
             c = lay.arena.classes
             plan.pre_launches.append(dict(
                 variant=TABLES, module=modules['tables'],

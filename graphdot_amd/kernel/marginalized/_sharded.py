@@ -336,37 +336,19 @@ def measured_shard_plan(backend, graphs, node_kernel, edge_kernel, jobs, nX,
     (`cost_table`), and the ranks take contiguous blocks of that order with
     equal predicted time.  Host only and deterministic: every rank computes
     the same plan."""
-    edge_kernel_in = edge_kernel
-    dgraphs, edge_kernel, C, fields = backend._graphs_and_kernels(
-        graphs, node_kernel, edge_kernel, traits)
-    arena = backend._host_arena(dgraphs, fields)     # (host only: no upload)
-    tab_bytes = backend._table_bytes(arena)
-    gtab = backend._global_tables(arena)
     jobs = np.ascontiguousarray(jobs)
-    # (the classification `prepare` itself makes: nodal traits size the LDS
-    # regions differently, a label-blind edge kernel adds the MFMA variant --
-    # without them the merge map, and with it which solver a pair runs on,
-    # differed from a plain HIPBackend's for such calls)
-    part = backend._partition(dgraphs, jobs, C, tab_bytes, gtab,
-                              nodal=traits.nodal is not False,
-                              mfma=backend._label_blind(edge_kernel_in))
-    # Plain value calls run on the twin-leaf quotient images where a plain
-    # HIPBackend takes them for the WHOLE list (DESIGN 4a): decided here, with
-    # the launch merging of the quotient list, and applied by every rank.
-    # (The cuts and the predicted times stay those of the full images: the
-    # cost table knows their variants, and the ranks re-balance by
-    # measurement.)
-    quotient = None
-    qgraphs = backend._quotient_graphs(graphs, dgraphs, traits, C)
-    if qgraphs is not None:
-        qarena = backend._host_arena(qgraphs, fields)
-        qpart = backend._partition(
-            qgraphs, jobs, C, backend._table_bytes(qarena),
-            backend._global_tables(qarena), nodal=False, mfma=False)
-        if backend._quotient_launches(qpart[3]):
-            quotient = dict(qpart.merge_map)
-    _, used, order_all, launches = part
-    merge_map = dict(part.merge_map)
+    # the host plans `prepare` itself chooses from (host only: no upload);
+    # the last is that of the full images.  The first is that of the
+    # twin-leaf quotient images where a plain HIPBackend takes them for the
+    # WHOLE list (DESIGN 4a): decided here, with their launch merging, and
+    # applied by every rank.  (Cuts and predicted times stay those of the
+    # full images: the cost table knows their variants, and the ranks
+    # re-balance by measurement.)
+    plans = list(backend._host_plans(graphs, node_kernel, edge_kernel, jobs,
+                                     traits))
+    quotient = dict(plans[0].part.merge_map) if plans[0].shape.quot else None
+    dgraphs, C, part = plans[-1].dgraphs, plans[-1].shape.C, plans[-1].part
+    order_all, launches, merge_map = part[2], part[3], dict(part.merge_map)
     ji, jj = jobs['i'].astype(np.int64), jobs['j'].astype(np.int64)
     n_node = np.array([g.n_node for g in dgraphs], np.int64)
     n_nz = np.array([g.n_nz for g in dgraphs], np.int64)
@@ -809,10 +791,10 @@ def distributed_backend(**kwargs):
             # variants and times per pair, hence different plans)
             key = (tuple(map(id, dgraphs)), id(jobs) if not
                    jobs.flags.writeable else hash(jobs.tobytes()),
-                   nX, nY, bool(traits.symmetric),
-                   traits.eval_gradient is True, rank, world,
-                   traits.nodal is not False,
-                   self._label_blind(edge_kernel))
+                   nX, nY, bool(traits.symmetric), rank, world,
+                   self._call_shape(None, traits,
+                                    1 + (traits.eval_gradient is True),
+                                    edge_kernel))
             hit = self._shard_plans.get(key)
             if hit is None:
                 if len(self._shard_plans) > 8:

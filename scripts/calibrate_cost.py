@@ -66,8 +66,8 @@ for real, f in ((np.float64, 'f64'), (np.float32, 'f32')):
         b = HIPBackend(real=real, min_launch=0)
         k = MarginalizedGraphKernel(kn, ke, q=q, backend=b)
         traits = k.traits(symmetric=True, eval_gradient=grad)
-        dgraphs, _, jobs2, C_, used, order_all, launches, _ = b._frontend(
-            G, kn, ke, k.p, jobs, traits)
+        host = next(b._host_plans(G, kn, ke, jobs, traits))
+        dgraphs, (jobs2, used, order_all, launches) = host.dgraphs, host.part
         n_node = np.array([g.n_node for g in dgraphs], np.int64)
         n_nz = np.array([g.n_nz for g in dgraphs], np.int64)
         slopes = []

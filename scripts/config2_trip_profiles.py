@@ -63,8 +63,8 @@ def main():
     # the product's own assignment of every pair to a solver variant (host only)
     dgraphs, ek, C, fields = backend._graphs_and_kernels(graphs, knode, kedge, traits)
     arena = backend._host_arena(dgraphs, fields)
-    part = backend._partition(dgraphs, jobs, C, backend._table_bytes(arena),
-                              backend._global_tables(arena))
+    part = backend._partition(dgraphs, jobs, backend._call_shape(
+        arena, traits, C, kedge))
     _, used, order_all, launches = part
     hists = np.array([np.bincount(np.diff(np.asarray(g.rowptr, dtype=np.int64)), minlength=17)
                       for g in dgraphs])

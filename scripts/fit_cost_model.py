@@ -26,8 +26,8 @@ for real, name in ((np.float64, 'f64'), (np.float32, 'f32')):
     jobs = np.column_stack((i, j)).astype(np.uint32).ravel().view(
         np.dtype([('i', np.uint32), ('j', np.uint32)]))
     traits = k.traits(symmetric=True, eval_gradient=False)
-    dgraphs, _, jobs2, C, used, order_all, launches, _ = b._frontend(
-        G, kn, ke, k.p, jobs, traits)
+    host = next(b._host_plans(G, kn, ke, jobs, traits))
+    dgraphs, (jobs2, used, order_all, launches) = host.dgraphs, host.part
     n_node = np.array([g.n_node for g in dgraphs])
     n_nz = np.array([g.n_nz for g in dgraphs])
     line = json.loads(open(os.path.join(

@@ -26,7 +26,7 @@ for trial in range(3):
     t2 = time.perf_counter()
     arena = b._host_arena(dgraphs, fields)
     t3 = time.perf_counter()
-    out = b._partition(dgraphs, jobs, C, b._table_bytes(arena), b._global_tables(arena))
+    out = b._partition(dgraphs, jobs, b._call_shape(arena, k.traits(symmetric=True), C, ke))
     t4 = time.perf_counter()
     img = arena.relocated(1 << 40)
     t5 = time.perf_counter()
@@ -41,6 +41,6 @@ if '--profile' in sys.argv:
     pr = cProfile.Profile(); pr.enable()
     dgraphs, ek, C, fields = b._graphs_and_kernels(G, kn, ke, k.traits(symmetric=True))
     arena = b._host_arena(dgraphs, fields)
-    out = b._partition(dgraphs, jobs, C, b._table_bytes(arena), b._global_tables(arena))
+    out = b._partition(dgraphs, jobs, b._call_shape(arena, k.traits(symmetric=True), C, ke))
     pr.disable()
     pstats.Stats(pr).sort_stats('tottime').print_stats(25)

@@ -113,9 +113,11 @@ def sources(select=None):
                     graphs, knode, kedge, traits, None, ngrad)
                 arena = backend._host_arena(dgraphs, fields)
                 # (the nodal-gradient and maximin solvers evaluate the
-                # microkernels directly: HIPBackend._layout)
-                gtab = backend._global_tables(arena) and not ngrad \
-                    and not maximin
+                # microkernels directly: HIPBackend._call_shape, which keeps
+                # the global tables of a maximin call without a gradient --
+                # the matrix does not: DESIGN.md, "The host plan of a call")
+                gtab = backend._call_shape(arena, traits, C, kedge, ngrad,
+                                           maximin).gtab and not maximin
                 todo = [(v, gtab) for v in oc
                         if not (v.S == 0 and C == 2 and nodal)]
                 if not (ngrad or maximin):

@@ -545,6 +545,7 @@ def test_measured_shard_plan_is_host_only_and_covers_every_job():
     shard, every shard holds few solver variants, the predicted times are
     balanced, the plan is the same on every rank, and the merge map is the
     single-GPU one."""
+    from graphdot_amd.kernel.marginalized._backend_hip import CallShape
     from graphdot_amd.kernel.marginalized._sharded import (
         measured_shard_plan, cost_table, variant_key)
     # (large enough that the pairs, not the launch tails, are what is dealt:
@@ -570,15 +571,15 @@ def test_measured_shard_plan_is_host_only_and_covers_every_job():
     dgs, ek, C, fields = b._graphs_and_kernels(G, kn, ke,
                                                k.traits(symmetric=True))
     arena = b._host_arena(dgs, fields)
-    whole = b._partition(dgs, jobs, C, 0, b._global_tables(arena))
+    shape = CallShape(C, gtab=b._global_tables(arena))
+    whole = b._partition(dgs, jobs, shape)
     assert sp.merge_map == whole.merge_map
     # a shard laid out with that map uses only variants the whole list uses
-    _, used_all, _, _ = b._partition(dgs, jobs, C, 0,
-                                     b._global_tables(arena))
+    _, used_all, _, _ = b._partition(dgs, jobs, shape)
     for s in sp.shards:
         _, used, order, launches = b._partition(
-            dgs, np.ascontiguousarray(jobs[s]), C, 0,
-            b._global_tables(arena), merge_map=sp.merge_map)
+            dgs, np.ascontiguousarray(jobs[s]), shape,
+            merge_map=sp.merge_map)
         assert set(used) <= set(used_all)
         assert sum(L['count'] for L in launches) == len(s)
     assert variant_key(b.variants[used_all[0]]).startswith('oc4_W1_')
@@ -678,17 +679,19 @@ def test_a_launch_is_sized_for_two_maxima_and_must_still_fit_the_lds():
     `_fit_launches_into_lds` hands pairs that hold a maximum to the general
     solver until the launch fits."""
     from graphdot_amd.kernel.marginalized._backend_hip import (
-        GENERAL, HIPBackend, LDS_LIMIT, NotOwnerComputes, OCVariant, Variant)
+        CallShape, GENERAL, HIPBackend, LDS_LIMIT, NotOwnerComputes,
+        OCVariant, Variant)
     be = HIPBackend(real=np.float64)
     g = be.variants.index(GENERAL)
     C, rsize = 1, 8
+    shape = CallShape(C)
     for v in (OCVariant(16, 64, 3, 8), Variant(16, 64, 8)):
         k = be.variants.index(v)
         if isinstance(v, OCVariant):
             assert be.lds_slot_bytes(v, C) == 10 * 64 * 16 * 8
 
         def need(idx, vec, img):
-            return be._launch_lds(v, C, vec[idx], vec[idx], img[idx], img[idx], 0)
+            return be._launch_lds(v, shape, vec[idx], vec[idx], img[idx], img[idx])
         room = LDS_LIMIT - int(be.lds_bytes(v, C, 0, 0))      # vector + 2 images
         # pair 0: long vector, small images; pair 1: short vector, large
         # images; pair 2: small in both.  0 and 1 fit alone, not together.
@@ -699,17 +702,18 @@ def test_a_launch_is_sized_for_two_maxima_and_must_still_fit_the_lds():
         assert need([2], vec, img) <= LDS_LIMIT
         assert need([0, 1, 2], vec, img) > LDS_LIMIT
         choice = np.full(3, k, dtype=np.int64)
-        out = be._fit_launches_into_lds(choice, C, vec, vec, img, img, 0, False)
+        out = be._fit_launches_into_lds(choice, shape, vec, vec, img, img)
         assert sorted(out.tolist()) == sorted([k, k, g])
         kept = np.flatnonzero(out == k)
         assert 2 in kept and need(kept, vec, img) <= LDS_LIMIT
         assert np.array_equal(choice, [k, k, k])            # (input untouched)
         # nothing to do: the same array comes back
-        assert be._fit_launches_into_lds(out, C, vec, vec, img, img, 0,
-                                         False) is out
+        assert be._fit_launches_into_lds(out, shape, vec, vec, img,
+                                         img) is out
         # calls that only the owner-computes solvers serve cannot fall back
         with pytest.raises(NotOwnerComputes):
-            be._fit_launches_into_lds(choice, C, vec, vec, img, img, 0, True)
+            be._fit_launches_into_lds(choice, shape._replace(oc_only=True),
+                                      vec, vec, img, img)
 
 
 def test_workgroups_per_pair_of_the_streamed_solver():

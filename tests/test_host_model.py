@@ -428,7 +428,7 @@ def test_native_job_layout_equals_the_numpy_restatement():
     import cases
     from graphdot_amd.kernel.marginalized import MarginalizedGraphKernel
     from graphdot_amd.kernel.marginalized._backend_hip import (
-        HIPBackend, VARIANTS, OC_VARIANTS, GENERAL)
+        CallShape, HIPBackend, VARIANTS, OC_VARIANTS, GENERAL)
     job_t = np.dtype([('i', np.uint32), ('j', np.uint32)])
 
     def triu(n):
@@ -456,8 +456,8 @@ def test_native_job_layout_equals_the_numpy_restatement():
                             dgs, _, _, fields = b._graphs_and_kernels(
                                 G, kn, ke, k.traits(symmetric=True))
                             arena = b._host_arena(dgs, fields)
-                            out.append(b._partition(
-                                dgs, jobs, C, 0, b._global_tables(arena)))
+                            out.append(b._partition(dgs, jobs, CallShape(
+                                C, gtab=b._global_tables(arena))))
                         (_, ua, oa, La), (_, ub, ob, Lb) = out
                         assert ua == ub and La == Lb
                         assert np.array_equal(oa, ob)
@@ -642,15 +642,17 @@ def _host_half_of_prepare(backend, graphs, node_kernel, edge_kernel, p, jobs,
     dgraphs, ek, C, fields = backend._graphs_and_kernels(
         graphs, node_kernel, edge_kernel, traits, None, ngrad)
     arena = backend._host_arena(dgraphs, fields)
-    tab_bytes = 0 if ngrad else backend._table_bytes(arena)
-    gtab = backend._global_tables(arena) and not ngrad
-    _, used, order_all, launches = backend._partition(
-        dgraphs, jobs, C, tab_bytes, gtab, oc_only=ngrad)
+    # (without the MFMA variant, as this test always was)
+    shape = backend._call_shape(arena, traits, C, edge_kernel,
+                                ngrad)._replace(mfma=False)
+    assert shape == (C, traits.nodal is not False, ngrad, 0, False,
+                     0 if ngrad else backend._table_bytes(arena),
+                     backend._global_tables(arena) and not ngrad, ngrad,
+                     False)
+    _, used, order_all, launches = backend._partition(dgraphs, jobs, shape)
     assert sorted(order_all.tolist()) == list(range(len(jobs)))
     assert sum(L['count'] for L in launches) == len(jobs)
-    sources = backend._sources(used, node_kernel, ek, p, dgraphs, C,
-                               traits.nodal is not False, tab_bytes > 0,
-                               gtab, ngrad)
+    sources = backend._sources(used, node_kernel, ek, p, dgraphs, shape)
     paths = jit.compile_many(list(sources.values()), backend.hipcc_extra)
     assert len(paths) == len(sources) and all(map(os.path.getsize, paths))
     return {field: _struct_values(pack_theta(obj, backend.real)[1])

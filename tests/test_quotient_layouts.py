@@ -9,7 +9,7 @@ import pytest
 import cases
 from graphdot_amd.graph import Graph
 from graphdot_amd.kernel.marginalized._backend_hip import (
-    HIPBackend, OCVariant, OC_QUOTIENT_LAYOUTS)
+    CallShape, HIPBackend, OCVariant, OC_QUOTIENT_LAYOUTS)
 from graphdot_amd.kernel.marginalized._devicegraph import (
     pack_many, quotient_graph)
 from test_quotient import hand_built, molecule
@@ -144,7 +144,8 @@ def test_merged_launches_hold_their_pairs(small, min_launch):
     out = []
     for native in (True, False):
         b = HIPBackend(real=np.float64, native=native, min_launch=min_launch)
-        _, used, order, launches = b._partition(qs, jobs, 1, 0, True)
+        _, used, order, launches = b._partition(
+                qs, jobs, CallShape(1, quot=True, gtab=True))
         seen = 0
         for L in launches:
             for t in order[L['offset']:L['offset'] + L['count']].tolist():
@@ -180,7 +181,8 @@ def test_p_holds_every_pair_in_the_roles_the_kernel_gives_it(small, seed,
         for native in (True, False):
             b = HIPBackend(real=np.float64, native=native,
                            min_launch=min_launch)
-            _, _, order, launches = b._partition(qs, jobs, 1, 0, True)
+            _, _, order, launches = b._partition(
+                qs, jobs, CallShape(1, quot=True, gtab=True))
             swapped[name] = 0
             for v, cells, t, flip, top in p_cells(launches, order, jobs, qs):
                 assert np.all(top < cells), (name, v, cells, int(top.max()))
