@@ -9,34 +9,18 @@ reduction), no host synchronisation and nothing of size n x n written.
 restatement the kernels are compared with, and the path of CPU tensors and of
 more than `KMAX` target columns."""
 import numpy as np
-from ...hip.source_module import STATIC, chunk, current_stream, suffix
-from ..gaussian_process._outlier import plane_strides
+from ...hip.source_module import STATIC, current_stream, suffix
+from .._dense_host import (_contract_planes, matrix_strides, plane_strides,
+                           triangle_grid)
 
 _module = STATIC['alignment.hip']
 precompile = _module.precompile
 _BLOCK = 256
 _WAVES = 4          # indices per workgroup of ka_rows (one per wave)
-_TILE = 64          # rows and columns per tile of ka_planes
 #: most target columns of the fused path (KT of alignment.hip)
 KMAX = 16
-
-
-def grid(n, nt):
-    """(chunk size KC, tiles on and above the diagonal, chunks): ka_planes
-    runs tiles x chunks workgroups.  A function of the shapes alone, so that
-    the order of every sum is the same on every call."""
-    kc = chunk(nt)
-    nb = -(-n // _TILE)
-    return kc, nb * (nb + 1) // 2, max(1, -(-nt // kc))
-
-
-def matrix_strides(K):
-    """(k_lane, k_col) in elements: the lane axis is the one with the smaller
-    stride (the matrix is symmetric)."""
-    s0, s1 = K.stride()
-    if K.shape[0] <= 1:
-        s0 = s1 = 0
-    return (s0, s1) if s0 <= s1 else (s1, s0)
+#: ka_planes runs tiles x chunks workgroups
+grid = triangle_grid
 
 
 def _check(K, Tc, P, planes):
@@ -128,7 +112,6 @@ def alignment_torch(K, Tc, P=None, planes=()):
     columns (the restatement stores K_c and w, which the kernels form on the
     fly)."""
     import torch
-    from ..gaussian_process.gpr import _contract_planes
     n, kt, planes = _check(K, Tc, P, planes)
     dev = K.device
     Kd = K.to(torch.float64)

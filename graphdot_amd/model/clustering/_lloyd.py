@@ -12,7 +12,7 @@ per-row-block shares ``part = [T (k) | counts (k)]`` are (R, row blocks, 2 k),
 added up by every consumer in the same fixed order."""
 import numpy as np
 from ...hip.source_module import STATIC, chunk, current_stream, suffix
-from ..decomposition._subspace import _check_K, _f64
+from .._dense_host import _check_K, _f64
 
 _module = STATIC['lloyd.hip']
 precompile = _module.precompile

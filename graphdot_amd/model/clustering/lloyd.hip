@@ -51,10 +51,6 @@
 #define RW (ROWS / NWAVE)        // rows per wave, all at once
 #define EPS 2.220446049250313e-16
 
-__device__ __forceinline__ bool is_finite(double x) {
-    return fabs(x) < __builtin_inf();
-}
-
 // gridDim.x = R
 template <typename T>
 __device__ __forceinline__ void seed_stage(
@@ -168,19 +164,6 @@ extern "C" __global__ __launch_bounds__(BLOCK) void
 kkm_seed_f64(const double *K, int64_t n, int k, int mode, const double *u,
              int *seeds, int *lab, double *mind) {
     seed_stage<double>(K, n, k, mode, u, seeds, lab, mind);
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_k(const T *p, double (&out)[VEC]) {
-    if constexpr (VEC == 1) {
-        out[0] = (double)p[0];
-    } else if constexpr (sizeof(T) == 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(p);
-        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-    } else {
-        const double2 v = *reinterpret_cast<const double2 *>(p);
-        out[0] = v.x; out[1] = v.y;
-    }
 }
 
 // lane l takes columns j = VEC (l + 64 t) + v

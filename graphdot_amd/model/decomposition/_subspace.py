@@ -13,6 +13,7 @@ fixed order (`col_stats_torch`) and applies on load."""
 import warnings
 import numpy as np
 from ...hip.source_module import STATIC, chunk, current_stream, suffix
+from .._dense_host import _check_K, _f64
 
 _module = STATIC['subspace.hip']
 precompile = _module.precompile
@@ -40,31 +41,6 @@ def grid(n, m):
     every sum is the same on every call."""
     kc = chunk(m)
     return kc, -(-n // _ROWS), max(1, -(-m // kc))
-
-
-def _f64(name, t, shape, dev):
-    import torch
-    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) \
-            or t.device != dev:
-        raise TypeError(f'{name}: {tuple(shape)} float64 on {dev} expected')
-    return t.contiguous()
-
-
-def _check_K(K):
-    """n of a symmetric matrix the kernels can read as it lies."""
-    import torch
-    if not K.is_cuda:
-        raise TypeError('K: a CUDA tensor expected; see the *_torch '
-                        'restatements')
-    if K.dim() != 2 or K.shape[0] != K.shape[1] \
-            or K.dtype not in (torch.float32, torch.float64):
-        raise TypeError('K: (n, n) float32 or float64 expected')
-    n = K.shape[0]
-    if n > 1 and K.stride() not in ((n, 1), (1, n)):
-        raise ValueError('K must be contiguous along one of its indices')
-    if K.data_ptr() % 16:
-        raise ValueError('K must be 16-byte aligned')
-    return n
 
 
 def _check_block(V, vpart, n, dev):

@@ -75,19 +75,6 @@ __device__ __forceinline__ void col_stats(
     }
 }
 
-template <typename T, int VEC>
-__device__ __forceinline__ void load_k(const T *p, double (&out)[VEC]) {
-    if constexpr (VEC == 1) {
-        out[0] = (double)p[0];
-    } else if constexpr (sizeof(T) == 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(p);
-        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-    } else {
-        const double2 v = *reinterpret_cast<const double2 *>(p);
-        out[0] = v.x; out[1] = v.y;
-    }
-}
-
 // the products of one tile: lane l takes columns jj = VEC (l + 64 t) + v
 template <typename T, int KC, int VEC>
 __device__ __forceinline__ void apply_tile(

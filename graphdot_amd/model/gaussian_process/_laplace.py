@@ -6,24 +6,16 @@ operations around them.  No launch here synchronises with the host.  Every
 launch has a ``*_torch`` restatement on any device: the yardstick of the
 kernels and the host path of the classifier."""
 import numpy as np
-from ...hip.source_module import STATIC, chunk, current_stream, suffix
-from ._outlier import plane_strides
+from ...hip.source_module import STATIC, current_stream, suffix
+from .._dense_host import _contract_planes, plane_strides, triangle_grid
 
 _module = STATIC['laplace.hip']
 precompile = _module.precompile
 _BLOCK = 256
 _WAVES = 4          # rows per workgroup of lp_build / lp_solve / lp_apply
-_TILE = 64          # rows and columns per tile of lp_planes
 _SUB = 4            # workgroups per tile (TILE / SUB columns each)
-
-
-def grid(n, nt):
-    """(chunk size KC, tiles on and above the diagonal, chunks): lp_planes
-    runs tiles x SUB x chunks workgroups.  A function of the shapes alone,
-    so that the order of every sum is the same on every call."""
-    kc = chunk(nt)
-    nb = -(-n // _TILE)
-    return kc, nb * (nb + 1) // 2, max(1, -(-nt // kc))
+#: lp_planes runs tiles x SUB x chunks workgroups
+grid = triangle_grid
 
 
 def _square(name, A, n):
@@ -198,7 +190,6 @@ def weights_torch(Binv, s, a, u, g):
 
 def contract_torch(P, planes, Binv, s, a, u, g):
     import torch
-    from .gpr import _contract_planes
     planes = np.asarray(planes, dtype=np.int64).ravel()
     if not len(planes):
         return torch.zeros(0, dtype=torch.float64, device=Binv.device)

@@ -5,34 +5,15 @@ the matrices' device, in stream order with the torch operations around them.
 Three launches per call (the rows of the inverse, the pass over the gradient
 planes, the fixed-order reduction) and no host synchronisation."""
 import numpy as np
-from ...hip.source_module import STATIC, chunk, current_stream, suffix
+from ...hip.source_module import STATIC, current_stream, suffix
+from .._dense_host import _contract_planes, plane_strides, triangle_grid
 
 _module = STATIC['outlier.hip']
 _BLOCK = 256
 _WAVES = 4          # rows per workgroup of od_rows (one per wave)
-_TILE = 64          # rows and columns per tile of od_planes
 _SUB = 4            # workgroups per tile (TILE / SUB columns each)
-
-
-def grid(n, nt):
-    """(chunk size KC, tiles on and above the diagonal, chunks): od_planes
-    runs tiles x SUB x chunks workgroups.  A function of the shapes alone,
-    so that the order of every sum is the same on every call."""
-    kc = chunk(nt)
-    nb = -(-n // _TILE)
-    return kc, nb * (nb + 1) // 2, max(1, -(-nt // kc))
-
-
-def plane_strides(P):
-    """(s_lane, s_col, s_k) in elements: the lane axis is whichever of the
-    first two has the smaller stride (the planes are symmetric in them)."""
-    s0, s1, s2 = P.stride()
-    n = P.shape[0]
-    if n <= 1:
-        s0 = s1 = 0
-    if P.shape[2] <= 1:
-        s2 = 0
-    return (s0, s1, s2) if s0 <= s1 else (s1, s0, s2)
+#: od_planes runs tiles x SUB x chunks workgroups
+grid = triangle_grid
 
 
 def _check_square(name, A, n):
@@ -111,7 +92,6 @@ def epilogue_torch(Kinv, Ks, y, sigma2, P=None, planes=()):
     """The same buffer by torch on any device: the yardstick of the kernels
     and the CPU path of the detector."""
     import torch
-    from .gpr import _contract_planes
     dev = Kinv.device
     y = torch.as_tensor(y, dtype=torch.float64).to(dev)
     sigma2 = torch.as_tensor(sigma2, dtype=torch.float64).to(dev)

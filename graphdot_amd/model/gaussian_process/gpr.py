@@ -28,31 +28,13 @@ import warnings
 import numpy as np
 from .._device_kernel import (device_call, on_device, as_float64,
                               active_planes)
+from .._dense_host import _contract_planes
 from ._base import GaussianProcessRegressorBase
 
 
 def _torch():
     import torch
     return torch
-
-
-def _contract_planes(W, dK):
-    """``sum_ij W[i, j] dK[i, j, k]`` for a *symmetric* W.  The kernel hands
-    its gradient over plane by plane (element (i, j, k) at i + n j + n^2 k,
-    reference _kernel.py:249-256): then the contraction is one matrix-vector
-    product over contiguous rows, 0.03 ms for n = 1000 and six planes on an
-    MI355X against 0.34 ms for multiply + reduce over the broadcast product
-    (scripts/time_gpr_dense.py).  Any other layout: multiply + reduce (the
-    einsum / GEMV form on a hyperparameter-fastest layout took 107 ms on
-    rocBLAS)."""
-    n0, n1, nt = dK.shape
-    planes = dK.permute(2, 1, 0)                # [k][j][i]: W_ji = W_ij
-    if planes.is_contiguous():
-        return planes.reshape(nt, n0 * n1) @ W.reshape(n0 * n1)
-    if dK.permute(2, 0, 1).is_contiguous():     # [k][i][j]
-        return dK.permute(2, 0, 1).reshape(nt, n0 * n1) @ \
-            W.contiguous().reshape(n0 * n1)
-    return (W.unsqueeze(-1) * dK).sum((0, 1))
 
 
 def _contract_local(W, lg, keep=None):

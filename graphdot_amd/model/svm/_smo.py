@@ -24,7 +24,7 @@ on svr.hip (`smo2`, `smo2_torch`), whose 2n variables
 over the n samples take 32 bytes of LDS per sample: ``NMAX2 = NMAX // 2``."""
 import numpy as np
 from ...hip.source_module import STATIC, chunk, current_stream, suffix
-from ..decomposition._subspace import _check_K, _f64
+from .._dense_host import _check_K, _f64
 
 _module = STATIC['smo.hip']
 precompile = _module.precompile
@@ -72,15 +72,21 @@ def _check_limits(tol, max_iter, steps=1):
             raise ValueError(f'{name}: a positive integer expected, got {v}')
 
 
+def _info0(P, device):
+    """info (P, 4) = [0, inf, -inf, 0] of a batch before its first step."""
+    import torch
+    info = torch.zeros((P, 4), dtype=torch.float64, device=device)
+    info[:, 1], info[:, 2] = float('inf'), float('-inf')
+    return info
+
+
 def start(P, n, device):
-    """(state (P, 2, n) = [alpha = 0 | G = -1], info (P, 4) = [0, inf, -inf,
-    0]) of a batch before its first step."""
+    """(state (P, 2, n) = [alpha = 0 | G = -1], `_info0`) of a batch before
+    its first step."""
     import torch
     state = torch.zeros((P, 2, n), dtype=torch.float64, device=device)
     state[:, 1] = -1.0
-    info = torch.zeros((P, 4), dtype=torch.float64, device=device)
-    info[:, 1], info[:, 2] = float('inf'), float('-inf')
-    return state, info
+    return state, _info0(P, device)
 
 
 def smo_slice(K, y, U, state, info, tol, steps, max_iter):
@@ -107,6 +113,18 @@ def smo_slice(K, y, U, state, info, tol, steps, max_iter):
     return state, info
 
 
+def _relaunch(launch, state, info, tol, max_iter):
+    """`launch()` advances `state` and `info` in place by a slice: again until
+    every problem has stopped, the host looking at `info` after each."""
+    slices = 0
+    while True:
+        launch()
+        slices += 1
+        if stopped(info.cpu().numpy(), tol, max_iter).all():
+            break
+    return Result(alpha=state[:, 0], G=state[:, 1], info=info, slices=slices)
+
+
 def smo(K, y, U, tol=1e-3, max_iter=1_000_000, steps=SLICE):
     """The batch solved by relaunching `svm_smo_*` until every problem has
     stopped (``m - M < tol``, `max_iter` steps, or a status): one download of
@@ -119,13 +137,9 @@ def smo(K, y, U, tol=1e-3, max_iter=1_000_000, steps=SLICE):
     _check_limits(tol, max_iter, steps)
     y, U = y.contiguous(), U.contiguous()
     state, info = start(P, n, K.device)
-    slices = 0
-    while True:
-        smo_slice(K, y, U, state, info, tol, steps, max_iter)
-        slices += 1
-        if stopped(info.cpu().numpy(), tol, max_iter).all():
-            break
-    return Result(alpha=state[:, 0], G=state[:, 1], info=info, slices=slices)
+    return _relaunch(
+        lambda: smo_slice(K, y, U, state, info, tol, steps, max_iter),
+        state, info, tol, max_iter)
 
 
 def _pair(ai, aj, Gi, Gj, Ui, Uj, differ, q):
@@ -166,30 +180,29 @@ def _pair(ai, aj, Gi, Gj, Ui, Uj, differ, q):
         torch.minimum(torch.clamp_min(nj, 0.0), Uj)
 
 
-def smo_torch(K, y, U, tol=1e-3, max_iter=1_000_000):
-    """The same rule with torch operations, all problems advancing together
-    (one that has stopped is left unchanged); one look per step."""
+def _loop_torch(K, s, U, state, info, tol, max_iter, rows):
+    """The same rule with torch operations on N variables with the signs `s`
+    (P, N) int8 and the bounds `U` (P, N), from a given `state` (P, 2, N) and
+    `info`, all problems advancing together (one that has stopped is left
+    unchanged); one look per step.  `rows(t)`: the (P, N) rows of the
+    variables `t` (P,); `K` gives the diagonal."""
     import torch
-    n = K.shape[0]
-    P = _check_batch(y, U, n)
-    _check_limits(tol, max_iter)
-    K = K.to(torch.float64)
+    P, N = s.shape
     dev = K.device
-    y, U = y.to(dev), U.to(dev)
-    diag = K.diagonal()
-    yf = y.to(torch.float64)
-    pos = y > 0
-    state, info = start(P, n, dev)
+    diag = K.diagonal().to(torch.float64)
+    diag = diag.repeat(N // len(diag))
+    sf = s.to(torch.float64)
+    pos = s > 0
     alpha, G = state[:, 0], state[:, 1]
-    inf = torch.full((P, n), float('inf'), dtype=torch.float64, device=dev)
-    done = torch.zeros(P, dtype=torch.float64, device=dev)
-    status = torch.zeros(P, dtype=torch.bool, device=dev)
+    inf = torch.full((P, N), float('inf'), dtype=torch.float64, device=dev)
+    done = info[:, 0].clone()
+    status = info[:, 3] != 0
     if not bool(torch.isfinite(diag).all()):
         status[:] = True
     col = torch.arange(P, device=dev)
     looks = 0
     while True:
-        v = -yf * G
+        v = -sf * G
         up = torch.where(pos, alpha < U, alpha > 0)
         low = torch.where(pos, alpha > 0, alpha < U)
         m, i = torch.where(up, v, -inf).max(1)       # (the first on a tie)
@@ -199,7 +212,7 @@ def smo_torch(K, y, U, tol=1e-3, max_iter=1_000_000):
         looks += 1
         if not bool(run.any()):
             break
-        Ki = K.index_select(0, i)
+        Ki = rows(i)
         b = m[:, None] - v
         a = (diag[i][:, None] + diag[None, :]) - 2.0 * Ki
         a = torch.where(a <= 0, torch.full_like(a, TAU), a)
@@ -207,23 +220,44 @@ def smo_torch(K, y, U, tol=1e-3, max_iter=1_000_000):
         obj = torch.where(cand, -(b * b) / a, inf)
         none = ~cand.any(1) | torch.isnan(obj).any(1)
         j = torch.where(torch.isnan(obj), inf, obj).argmin(1)
-        Kj = K.index_select(0, j)
+        Kj = rows(j)
         ai, aj = alpha[col, i], alpha[col, j]
         ni, nj = _pair(ai, aj, G[col, i], G[col, j], U[col, i], U[col, j],
-                       y[col, i] != y[col, j], a[col, j])
+                       s[col, i] != s[col, j], a[col, j])
         status |= run & none
         run &= ~none
         zero = torch.zeros_like(ai)
-        si = torch.where(run, yf[col, i] * (ni - ai), zero)
-        sj = torch.where(run, yf[col, j] * (nj - aj), zero)
+        si = torch.where(run, sf[col, i] * (ni - ai), zero)
+        sj = torch.where(run, sf[col, j] * (nj - aj), zero)
         alpha[col, i] = torch.where(run, ni, ai)
         alpha[col, j] = torch.where(run, nj, alpha[col, j])
         G[:] = torch.where(run[:, None],
-                           G + yf * (Ki * si[:, None] + Kj * sj[:, None]), G)
+                           G + sf * (Ki * si[:, None] + Kj * sj[:, None]), G)
         done += run.to(torch.float64)
     info[:, 0], info[:, 1], info[:, 2] = done, m, M
     info[:, 3] = status.to(torch.float64)
     return Result(alpha=alpha, G=G, info=info, slices=looks)
+
+
+def smo_torch(K, y, U, tol=1e-3, max_iter=1_000_000):
+    """`_loop_torch` on the n samples from `start`."""
+    import torch
+    n = K.shape[0]
+    P = _check_batch(y, U, n)
+    _check_limits(tol, max_iter)
+    K = K.to(torch.float64)
+    dev = K.device
+    return _loop_torch(K, y.to(dev), U.to(dev), *start(P, n, dev), tol,
+                       max_iter, lambda t: K.index_select(0, t))
+
+
+def _as_it_lies(K):
+    """K where the kernels can read it as it lies (contiguous along one index,
+    16-byte aligned: what `_check_K` asks for), else a copy that is."""
+    n = K.shape[0]
+    if n > 1 and K.stride() not in ((n, 1), (1, n)) or K.data_ptr() % 16:
+        return K.contiguous()
+    return K
 
 
 def solve(K, y, U, tol, max_iter):
@@ -231,9 +265,8 @@ def solve(K, y, U, tol, max_iter):
     anywhere else."""
     n = K.shape[0]
     if K.is_cuda and n <= NMAX:
-        if n > 1 and K.stride() not in ((n, 1), (1, n)) or K.data_ptr() % 16:
-            K = K.contiguous()
-        return smo(K, y.to(K.device), U.to(K.device), tol, max_iter), True
+        return smo(_as_it_lies(K), y.to(K.device), U.to(K.device), tol,
+                   max_iter), True
     return smo_torch(K, y, U, tol, max_iter), False
 
 
@@ -291,11 +324,6 @@ def _check_state(state, info, P, n, dev):
     return _f64('state', state, (P, 2, n), dev), _f64('info', info, (P, 4), dev)
 
 
-def _info0(P, device):
-    """info (P, 4) = [0, inf, -inf, 0] of a batch before its first step."""
-    return start(P, 0, device)[1]
-
-
 def smo_from(K, y, U, state, info, tol=1e-3, max_iter=1_000_000, steps=SLICE):
     """`smo` entered with a given `state` (P, 2, n) = [alpha | G] and `info`
     (both advanced in place): any linear term and any feasible start, for `G =
@@ -305,71 +333,9 @@ def smo_from(K, y, U, state, info, tol=1e-3, max_iter=1_000_000, steps=SLICE):
     _check_limits(tol, max_iter, steps)
     y, U = y.contiguous(), U.contiguous()
     state, info = _check_state(state, info, P, n, K.device)
-    slices = 0
-    while True:
-        smo_slice(K, y, U, state, info, tol, steps, max_iter)
-        slices += 1
-        if stopped(info.cpu().numpy(), tol, max_iter).all():
-            break
-    return Result(alpha=state[:, 0], G=state[:, 1], info=info, slices=slices)
-
-
-def _loop_torch(K, s, U, state, info, tol, max_iter, rows):
-    """The loop of `smo_torch` on N variables with the signs `s` (P, N) int8
-    and the bounds `U` (P, N), from a given `state` (P, 2, N) and `info`.
-    `rows(t)`: the (P, N) rows of the variables `t` (P,); `K` gives the
-    diagonal."""
-    import torch
-    P, N = s.shape
-    dev = K.device
-    diag = K.diagonal().to(torch.float64)
-    diag = diag.repeat(N // len(diag))
-    sf = s.to(torch.float64)
-    pos = s > 0
-    alpha, G = state[:, 0], state[:, 1]
-    inf = torch.full((P, N), float('inf'), dtype=torch.float64, device=dev)
-    done = info[:, 0].clone()
-    status = info[:, 3] != 0
-    if not bool(torch.isfinite(diag).all()):
-        status[:] = True
-    col = torch.arange(P, device=dev)
-    looks = 0
-    while True:
-        v = -sf * G
-        up = torch.where(pos, alpha < U, alpha > 0)
-        low = torch.where(pos, alpha > 0, alpha < U)
-        m, i = torch.where(up, v, -inf).max(1)       # (the first on a tie)
-        M = torch.where(low, v, inf).min(1).values
-        status |= ~torch.isfinite(G).all(1)
-        run = ~status & ~(m - M < tol) & (done < max_iter)
-        looks += 1
-        if not bool(run.any()):
-            break
-        Ki = rows(i)
-        b = m[:, None] - v
-        a = (diag[i][:, None] + diag[None, :]) - 2.0 * Ki
-        a = torch.where(a <= 0, torch.full_like(a, TAU), a)
-        cand = low & (v < m[:, None])
-        obj = torch.where(cand, -(b * b) / a, inf)
-        none = ~cand.any(1) | torch.isnan(obj).any(1)
-        j = torch.where(torch.isnan(obj), inf, obj).argmin(1)
-        Kj = rows(j)
-        ai, aj = alpha[col, i], alpha[col, j]
-        ni, nj = _pair(ai, aj, G[col, i], G[col, j], U[col, i], U[col, j],
-                       s[col, i] != s[col, j], a[col, j])
-        status |= run & none
-        run &= ~none
-        zero = torch.zeros_like(ai)
-        si = torch.where(run, sf[col, i] * (ni - ai), zero)
-        sj = torch.where(run, sf[col, j] * (nj - aj), zero)
-        alpha[col, i] = torch.where(run, ni, ai)
-        alpha[col, j] = torch.where(run, nj, alpha[col, j])
-        G[:] = torch.where(run[:, None],
-                           G + sf * (Ki * si[:, None] + Kj * sj[:, None]), G)
-        done += run.to(torch.float64)
-    info[:, 0], info[:, 1], info[:, 2] = done, m, M
-    info[:, 3] = status.to(torch.float64)
-    return Result(alpha=alpha, G=G, info=info, slices=looks)
+    return _relaunch(
+        lambda: smo_slice(K, y, U, state, info, tol, steps, max_iter),
+        state, info, tol, max_iter)
 
 
 def smo_torch_from(K, y, U, state, info, tol=1e-3, max_iter=1_000_000):
@@ -392,10 +358,8 @@ def solve_from(K, y, U, state, info, tol, max_iter):
     n = K.shape[0]
     dev = K.device
     if K.is_cuda and n <= NMAX:
-        if n > 1 and K.stride() not in ((n, 1), (1, n)) or K.data_ptr() % 16:
-            K = K.contiguous()
-        return smo_from(K, y.to(dev), U.to(dev), state, info, tol,
-                        max_iter), True
+        return smo_from(_as_it_lies(K), y.to(dev), U.to(dev), state, info,
+                        tol, max_iter), True
     return smo_torch_from(K, y, U, state, info, tol, max_iter), False
 
 
@@ -514,13 +478,9 @@ def smo2(K, U, z, eps, tol=1e-3, max_iter=1_000_000, steps=SLICE):
     state, info = start2(z, eps, K.device)
     if state.shape != (P, 2, 2 * n):
         raise TypeError(f'z: ({P}, {n}) float64 expected')
-    slices = 0
-    while True:
-        smo2_slice(K, U, state, info, tol, steps, max_iter)
-        slices += 1
-        if stopped(info.cpu().numpy(), tol, max_iter).all():
-            break
-    return Result(alpha=state[:, 0], G=state[:, 1], info=info, slices=slices)
+    return _relaunch(
+        lambda: smo2_slice(K, U, state, info, tol, steps, max_iter),
+        state, info, tol, max_iter)
 
 
 def smo2_torch(K, U, z, eps, tol=1e-3, max_iter=1_000_000):
@@ -547,7 +507,6 @@ def solve2(K, U, z, eps, tol, max_iter):
     anywhere else."""
     n = K.shape[0]
     if K.is_cuda and n <= NMAX2:
-        if n > 1 and K.stride() not in ((n, 1), (1, n)) or K.data_ptr() % 16:
-            K = K.contiguous()
-        return smo2(K, U.to(K.device), z, eps, tol, max_iter), True
+        return smo2(_as_it_lies(K), U.to(K.device), z, eps, tol,
+                    max_iter), True
     return smo2_torch(K, U, z, eps, tol, max_iter), False

@@ -55,10 +55,6 @@
 #define TAU 1e-12
 #define NONE 0x7fffffff          // the index of an empty choice
 
-__device__ __forceinline__ bool is_finite(double x) {
-    return fabs(x) < __builtin_inf();
-}
-
 // what the waves exchange: stage 1 [m, M, alpha_i, U_i, K_ii], i;
 // stage 2 [objective, G_j, alpha_j, U_j, a_j], j
 struct Exchange {
@@ -221,40 +217,8 @@ __device__ __forceinline__ void smo2_slice(
             kj[k] = r < n ? (double)rowj[r] : 0.0;
         }
 
-        // -- the pair along the constraint, clipped to its box (libsvm's two
-        // cases; the last clamp guards the partner, a rounded difference)
-        double ni, nj;
-        if (pos_i != pos_j) {
-            const double delta = (-G_i - G_j) / q, diff = a_i - a_j;
-            ni = a_i + delta;
-            nj = a_j + delta;
-            if (diff > 0.0) {
-                if (nj < 0.0) { nj = 0.0; ni = diff; }
-            } else {
-                if (ni < 0.0) { ni = 0.0; nj = -diff; }
-            }
-            if (diff > U_i - U_j) {
-                if (ni > U_i) { ni = U_i; nj = U_i - diff; }
-            } else {
-                if (nj > U_j) { nj = U_j; ni = U_j + diff; }
-            }
-        } else {
-            const double delta = (G_i - G_j) / q, sum = a_i + a_j;
-            ni = a_i - delta;
-            nj = a_j + delta;
-            if (sum > U_i) {
-                if (ni > U_i) { ni = U_i; nj = sum - U_i; }
-            } else {
-                if (nj < 0.0) { nj = 0.0; ni = sum; }
-            }
-            if (sum > U_j) {
-                if (nj > U_j) { nj = U_j; ni = sum - U_j; }
-            } else {
-                if (ni < 0.0) { ni = 0.0; nj = sum; }
-            }
-        }
-        ni = ni < 0.0 ? 0.0 : (ni > U_i ? U_i : ni);
-        nj = nj < 0.0 ? 0.0 : (nj > U_j ? U_j : nj);
+        // -- the pair along the constraint, clipped to its box: ni, nj
+        SMO_PAIR_UPDATE(pos_i != pos_j, a_i, a_j, G_i, G_j, U_i, U_j, q);
         const double s_i = pos_i ? ni - a_i : -(ni - a_i),
                      s_j = pos_j ? nj - a_j : -(nj - a_j);
         if (tid == ri % BLOCK) A[i] = ni;

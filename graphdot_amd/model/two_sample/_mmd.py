@@ -12,7 +12,7 @@ host and `statistics` turns the downloaded sums into the two estimators."""
 import numpy as np
 from ...hip.source_module import (
     CHUNKS, STATIC, chunk, current_stream, suffix)
-from ..alignment._align import matrix_strides
+from .._dense_host import matrix_strides
 
 _module = STATIC['mmd.hip']
 precompile = _module.precompile
