@@ -154,14 +154,16 @@ def sources(select=None):
                            tuple(backend.hipcc_extra), src)
 
 
-def compile_all(select=None, max_workers=None):
+def compile_all(select=None, max_workers=None, extra=()):
     """Compile the matrix into the JIT cache; returns (labels, failures)
-    with failures = [(label, hipcc diagnostics)]."""
+    with failures = [(label, hipcc diagnostics)].  `extra`: further (label,
+    flags, source) for the same pool (tests/menu_edges.py `sources()`)."""
+    import itertools
     import os
     from concurrent.futures import ThreadPoolExecutor
     from graphdot_amd.hip import jit
     items, seen = [], set()
-    for label, flags, src in sources(select):
+    for label, flags, src in itertools.chain(sources(select), extra):
         key = jit.cache_key(src, flags)
         if key not in seen:
             seen.add(key)
