@@ -52,10 +52,19 @@ def hipcc_version():
     return _version
 
 
+#: headers of DEVICE_INCLUDE that one translation unit alone includes (the
+#: text units of graphdot_amd.hip.source_module): such a header is digested
+#: into the key of the sources that name it and of no other, so that adding or
+#: editing one does not give every solver's code object a new key
+UNIT_HEADERS = ('knn.h',)
+
+
 def _headers_digest():
+    """Digest of the headers that the sources share: every ``*.h`` of
+    DEVICE_INCLUDE but the `UNIT_HEADERS`."""
     h = hashlib.sha256()
     for name in sorted(os.listdir(DEVICE_INCLUDE)):
-        if name.endswith('.h'):
+        if name.endswith('.h') and name not in UNIT_HEADERS:
             with open(os.path.join(DEVICE_INCLUDE, name), 'rb') as f:
                 h.update(name.encode())
                 h.update(f.read())
@@ -74,6 +83,11 @@ def cache_key(source, flags=()):
                  hipcc_version(), _hdr_digest):
         h.update(part.encode())
         h.update(b'\0')
+    for name in UNIT_HEADERS:
+        if f'#include "{name}"' in source:
+            with open(os.path.join(DEVICE_INCLUDE, name), 'rb') as f:
+                h.update(name.encode())
+                h.update(f.read())
     return h.hexdigest()[:32]
 
 

@@ -2,9 +2,11 @@
 models that use them): `SourceModule` compiles one HIP source into the JIT
 cache of `jit` and loads it once per process; `STATIC` lists the sources that
 are files of the package, each with its flags, for their host modules and for
-``__graft_entry__.build()``.  Below them, the few lines every torch-facing
-launch repeats.  Nothing here imports torch (or a package that does) at module
-level: `build()` compiles through this module before ``libgdhip.so`` is used.
+``__graft_entry__.build()``, and `TEXT_UNITS` those that are a device header
+of csrc/device and a few lines of text.  Below them, the few lines every
+torch-facing launch repeats.  Nothing here imports torch (or a package that
+does) at module level: `build()` compiles through this module before
+``libgdhip.so`` is used.
 """
 import os
 import struct
@@ -93,6 +95,41 @@ STATIC_SOURCES = (
 #: file name -> SourceModule
 STATIC = {os.path.basename(p): SourceModule(os.path.join(_PACKAGE, p))
           for p in STATIC_SOURCES}
+
+
+def _wrappers(*kernels):
+    """The ``extern "C"`` wrappers of a text unit: (name, device function,
+    parameters as 'type name, ...') each."""
+    out = []
+    for name, stage, params in kernels:
+        names = ', '.join(p.split()[-1].lstrip('*') for p in params.split(','))
+        out.append(f'extern "C" __global__ __launch_bounds__(BLOCK) void\n'
+                   f'{name}({params})\n{{\n    {stage}({names});\n}}\n')
+    return '\n'.join(out)
+
+
+_KNN_TOPK = ('int64_t b, int64_t n, int64_t s_row, int64_t s_col, '
+             'const double *dq, const double *dt, int k, int exclude_self, '
+             'int64_t parts, double *out_d2, int64_t *out_idx, int *flag')
+#: name -> SourceModule of the translation units that are text: a device
+#: header of csrc/device and the wrappers that name its kernels
+TEXT_UNITS = {'knn': SourceModule(source='#include "knn.h"\n\n' + _wrappers(
+    ('knn_topk_f32', 'knn::topk_stage<float>', 'const float *K, ' + _KNN_TOPK),
+    ('knn_topk_f64', 'knn::topk_stage<double>',
+     'const double *K, ' + _KNN_TOPK),
+    ('knn_merge', 'knn::merge_stage',
+     'const double *ws_d2, const int64_t *ws_idx, int64_t b, int64_t parts, '
+     'int k, double *out_d2, int64_t *out_idx'),
+    ('knn_average', 'knn::average_stage',
+     'const double *d2, const int64_t *idx, int64_t b, int k, '
+     'const double *T, int64_t n, int64_t m, int mode, double *out'),
+    ('knn_lrd', 'knn::lrd_stage',
+     'const double *d2, const int64_t *idx, int64_t b, int k, '
+     'const double *kdist, int64_t n, double *lrd'),
+    ('knn_ratio', 'knn::ratio_stage',
+     'const int64_t *idx, int64_t b, int k, const double *lrd_train, '
+     'int64_t n, const double *lrd, double *lof'),
+))}
 
 #: planes / candidates per register chunk (the template parameter KC of the
 #: kernels that keep a chunk of accumulators in registers)

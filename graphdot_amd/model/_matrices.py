@@ -1,7 +1,7 @@
 """The kernel matrices of the models that work on a whole Gram matrix where it
-lies (`KernelPCA`, `KernelKMeans`): a precomputed matrix as it was handed in,
-or the kernel's own -- adopted from its device path on a GPU (DESIGN.md
-section 25), evaluated on the host otherwise."""
+lies (`KernelPCA`, `KernelKMeans`, the neighbour models): a precomputed
+matrix as it was handed in, or the kernel's own -- adopted from its device
+path on a GPU, evaluated on the host otherwise."""
 import numpy as np
 from ._device_kernel import device_call, on_device
 
@@ -66,13 +66,31 @@ class KernelMatrices:
         return la.tensor(self.kernel(X, **self.kernel_options)), False
 
     def _cross(self, Z, device):
+        return self._cross_from(Z, device)[0]
+
+    def _cross_from(self, Z, device):
+        """(the cross matrix of `Z` against the training set on `device`,
+        from the device path?)"""
         if self._precomputed:
-            return self._given(Z, (None, self._n), device)
+            return self._given(Z, (None, self._n), device), False
         la = self._dense()
         if on_device(la, self.kernel_options) and device.type == 'cuda':
             Ks = device_call(self.kernel, 'device_cross_gram', Z, self.X)
             if Ks is not None:
-                return _torch().as_tensor(Ks, device=device)
+                return _torch().as_tensor(Ks, device=device), True
         Ks = np.asarray(self.kernel(Z, self.X, **self.kernel_options),
                         dtype=np.float64)
-        return _torch().from_numpy(np.ascontiguousarray(Ks)).to(device)
+        return _torch().from_numpy(np.ascontiguousarray(Ks)).to(device), False
+
+    def _self_similarity(self, Z, device):
+        """(b,) float64 k(z, z) of the graphs `Z` on `device`: from the
+        kernel's `device_diag` on a GPU, from `kernel.diag` otherwise."""
+        la = self._dense()
+        if on_device(la, self.kernel_options) and device.type == 'cuda':
+            d = device_call(self.kernel, 'device_diag', Z)
+            if d is not None:
+                return _torch().as_tensor(d, device=device).to(
+                    _torch().float64)
+        d = np.asarray(self.kernel.diag(Z, **self.kernel_options),
+                       dtype=np.float64)
+        return _torch().from_numpy(np.ascontiguousarray(d)).to(device)

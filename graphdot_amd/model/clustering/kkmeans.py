@@ -22,7 +22,6 @@ matrix.  Anywhere else the same chain runs through torch
 import time
 import warnings
 import numpy as np
-from .._device_kernel import device_call, on_device
 from .._matrices import KernelMatrices
 from . import _lloyd
 
@@ -162,17 +161,6 @@ class KernelKMeans(KernelMatrices):
         """(b,) the nearest cluster of each of the graphs `Z` (or of the rows
         of a precomputed (b, n) cross matrix)."""
         return self._nearest(Z)[1].cpu().numpy().astype(np.int64)
-
-    def _self_similarity(self, Z, device):
-        la = self._dense()
-        if on_device(la, self.kernel_options) and device.type == 'cuda':
-            d = device_call(self.kernel, 'device_diag', Z)
-            if d is not None:
-                return _torch().as_tensor(d, device=device).to(
-                    _torch().float64)
-        d = np.asarray(self.kernel.diag(Z, **self.kernel_options),
-                       dtype=np.float64)
-        return _torch().from_numpy(np.ascontiguousarray(d)).to(device)
 
     def transform(self, Z, diag=None):
         """(b, k) feature-space distances of the graphs `Z` to the cluster
