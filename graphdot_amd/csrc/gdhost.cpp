@@ -539,6 +539,8 @@ int gdh_classify_oc(int64_t n_pairs, const int32_t *ca, const int32_t *cb,
             const int64_t np_v = gu != gv ? std::max(np_, n2 * (n1 | 1)) : np_;
             if (N > T * R[v] || np_v >= (fly ? 0x3FFF : 0xFFFF)) continue;
             if (gu && (pmd_true > gu || std::min(maxdeg[a], maxdeg[b]) > gv)) continue;
+            // the LDS of the workgroup: kernel/marginalized/_menu.py, SolverMenu._pcap
+            // and _oc_lds (static + dynamic), restated
             const int64_t NR = T * R[v];
             const int64_t pcap = (np_v + 1 + 3) / 4 * 4;
             const int64_t NRy = ((n_L[v] > 0 && C != 2) || fly) ? 0 : NR;

@@ -897,6 +897,13 @@ def quotient_graph(dg, native=True):
     return q
 
 
+def quotient_images(dgraphs):
+    """Are the images of a call twin-leaf quotient images (`quotient_graph`:
+    all of a call's are, or none)?"""
+    return bool(len(dgraphs)
+                and getattr(dgraphs[0], 'n_orig', None) is not None)
+
+
 def class_bytes(n_node, n_nz):
     """Bytes of the label-class section that precedes a graph's blob in the
     arena: u8 node classes [pad4(n_node)] then u8 edge classes [pad4(n_nz)],
@@ -1075,8 +1082,8 @@ class GraphArena:
                                             dtype=np.int64)
         cbytes = class_bytes(feat['n_node'], feat['n_nz']) \
             if self.n else np.zeros(0, np.int64)
-        with_terms = bool(terms and cls is not None and self.n and getattr(
-            dgraphs[0], 'n_orig', None) is not None)
+        with_terms = bool(terms and cls is not None
+                          and quotient_images(dgraphs))
         tbytes = term_bytes(feat['n_nz']) if with_terms \
             else np.zeros(self.n, np.int64)
         ends = cursor + np.cumsum(sizes + cbytes + tbytes)
@@ -1133,7 +1140,7 @@ class GraphArena:
         if self.n:
             n_node, n_nz = feat['n_node'], feat['n_nz']
             hdr['n_node'], hdr['n_nz'] = n_node, n_nz
-            if getattr(dgraphs[0], 'n_orig', None) is not None:
+            if quotient_images(dgraphs):
                 # quotient images: the node count of the full graph in the
                 # high half of n_node (graph.h)
                 hdr['n_node'] = (n_node | (np.array(
