@@ -29,12 +29,23 @@ def column_major(K):
     return K.contiguous()
 
 
-def select(K, n, method, alpha=0.0, tol=0.0):
+def select(K, n, method, alpha=0.0, tol=0.0, state=None):
     """Greedy selection of `n` indices on the device.  `K`: square float32 or
     float64 CUDA tensor, symmetric (read as column-major; see
     `column_major`).  `method`: 'determinant' or 'variance' (`alpha` is then
     added to the diagonal as it is read).  Returns (picks as a numpy int64
-    array, status word)."""
+    array, status word).
+
+    `state`: a dict that receives the device tensors the loop worked on, as
+    the last launch left them, under the names `crit`, `V`, `W`, `chosen`,
+    `scal` and `partials` (for the tests; the models pass none, and nothing
+    is launched or waited for on its account).  Column s of `V` (Q or L) is
+    at s N; 'determinant' keeps row s of `W` (C) at s N, 'variance' one
+    column (p) in `W`.  The last pick gets no `al_update_argmax`: `crit` is
+    the criterion after n - 1 updates, column n - 1 of `V` the direction w
+    before its scaling (determinant; `scal[0]` = 1 / |w|, and row n - 1 of
+    `W` is not written) or the column l (variance; `W` is then the posterior
+    column p of the last pick)."""
     import numpy as np
     import torch
     K = column_major(K)
@@ -102,4 +113,7 @@ def select(K, n, method, alpha=0.0, tol=0.0):
     # the one download (it waits for the stream); the workspaces stay alive
     # until here, behind every launch that uses them
     out = iw.cpu().numpy()
+    if state is not None:
+        state.update(crit=crit, V=V, W=W, chosen=chosen, scal=scal,
+                     partials=partials)
     return out[4:].astype(np.int64), int(out[0])

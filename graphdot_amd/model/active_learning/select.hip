@@ -20,8 +20,11 @@
 //
 // The pivot stays in device memory (picks[]); no kernel needs the host.  The
 // argmax keeps the largest criterion and, among equal values, the smallest
-// index; a NaN never wins.  A pivot whose residual is not above `tol` times
-// its own size sets the status word and every later launch returns at once.
+// index.  A sample whose criterion is NaN is passed over like a chosen one --
+// never picked, and hiding no other, whichever lane holds it -- and when only
+// such samples are left the status word says so (the rule of
+// _greedy._argmax).  A pivot whose residual is not above `tol` times its own
+// size sets the status word and every later launch returns at once.
 #include "dense_reduce.h"
 
 #define CHUNK 1024   // coefficients staged in LDS per pass
@@ -53,11 +56,12 @@ __device__ double block_sum(double v, double *red) {
     return t;
 }
 
-// (value, index) order of the argmax: larger value first, then smaller index;
-// idx < 0 is "none" and a NaN value never beats anything
+// (value, index) order of the argmax: larger value first, then smaller index.
+// idx < 0 is "none"; a NaN candidate never wins, and a NaN incumbent (a lane
+// starts from its own criterion) loses to every candidate that is not NaN
 __device__ __forceinline__ bool better(double v, int i, double bv, int bi) {
-    if (i < 0) return false;
-    if (bi < 0) return v == v;
+    if (i < 0 || v != v) return false;
+    if (bi < 0 || bv != bv) return true;
     return v > bv || (v == bv && i < bi);
 }
 

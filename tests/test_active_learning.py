@@ -2,7 +2,11 @@
 reference's picks (golden/active_learning.json, made by
 golden/make_golden_active_learning.py), against plain float64 restatements of
 the greedy criteria written here, and -- on the GPU -- the device loops of
-select.hip against the host loops."""
+select.hip against the host loops.  The state of the two loops by its
+definition and by the loops' recurrence, with the bounds derived from their
+difference, is here as well: test_active_learning_gpu.py holds select.hip's
+state against it."""
+import functools
 import json
 import os
 import numpy as np
@@ -183,6 +187,241 @@ def test_cpu_torch_tensor_is_accepted():
     got = DeterminantMaximizer('precomputed', device='cpu')(
         torch.from_numpy(K), 8)
     assert got == want
+
+
+# ------------------------------------------------- the state of the two loops
+# What test_active_learning_gpu.py compares select.hip's state with.  Both
+# references take the stored matrix widened to double and the picks P they are
+# to follow (teacher-forced: a near-tie cannot turn a rounding difference
+# into another trajectory), and both return the state as `_select.select`
+# leaves it after len(P) picks -- the last pick gets no criterion update:
+#   determinant: crit (rho after n - 1 updates), Q (N, n - 1), C (n - 1, N),
+#                w (the last direction, not scaled), scal (1 / |w|)
+#   variance:    crit, L (N, n), p (the posterior column of the last pick)
+# and the criterion before every pick, hist (n, N).
+EPS = np.finfo(np.float64).eps
+#: the tolerance of the GPU tests: 8 x max(E_host, 4 eps) x scale, E_host the
+#: error of the recurrence (the host loops', restated) against the definition
+FACTOR, FLOOR = 8, 4 * EPS
+#: `spd` has a condition number of about 9: classical Gram-Schmidt loses
+#: orthogonality like cond^2 eps, and the restatement has to stay within
+#: 4 x that of the definition to be a yardstick at all
+E_HOST_CAP = 4 * 81 * EPS
+ALPHA = 1e-2        # of the variance cases: visible where it is forgotten
+
+
+@functools.lru_cache(maxsize=None)
+def spd(N, seed, dtype='float64'):
+    """A A^T / N + I / 2, A (N, N) standard normal, as stored in `dtype`
+    (exactly symmetric; read-only: shared among the tests)."""
+    A = np.random.default_rng(seed).standard_normal((N, N))
+    K = A @ A.T / N + 0.5 * np.eye(N)
+    K = (0.5 * (K + K.T)).astype(dtype)
+    K.setflags(write=False)
+    return K
+
+
+@functools.lru_cache(maxsize=None)
+def tie_matrix(name, dtype='float64'):
+    """'pairs': 260 blocks [[1, .5], [.5, 1]] (N = 520; all criteria equal
+    at the start, equal within the even and the odd samples afterwards);
+    'identity': I_600."""
+    K = np.kron(np.eye(260), [[1.0, 0.5], [0.5, 1.0]]) if name == 'pairs' \
+        else np.eye(600)
+    K = K.astype(dtype)
+    K.setflags(write=False)
+    return K
+
+
+#: (N, n) of the state tests: the smallest; the 64 rows of an al_colreduce
+#: pass on both sides ((64, 64): n == N); the block of 256 on both sides
+#: ((257, 257): a second block of one row, a last al_colreduce block with one
+#: live wave, n == N); three blocks
+SHAPES = [(1, 1), (2, 2), (63, 20), (64, 64), (65, 33), (255, 33), (256, 33),
+          (257, 257), (513, 40)]
+#: more picks than one pass of the coefficient staging holds (CHUNK of
+#: select.hip): steps 1024 and 1025 are the first with a full chunk and with
+#: a second chunk of one coefficient; 1040 = 4 x 256 + 16 rows
+BEYOND_ONE_CHUNK = (1040, 1028)
+
+
+def chunk_of_select_hip():
+    import re
+    import graphdot_amd.model.active_learning as al
+    path = os.path.join(os.path.dirname(al.__file__), 'select.hip')
+    with open(path) as f:
+        return int(re.search(r'^#define CHUNK (\d+)', f.read(), re.M).group(1))
+
+
+def define_state(K, P, method, alpha=0.0):
+    """The state by its definition (Householder QR of the chosen rows; the
+    Cholesky factor of the chosen block), not by the loops' recurrences."""
+    N, n = len(K), len(P)
+    P = np.asarray(P)
+    if method == 'determinant':
+        Qr, R = np.linalg.qr(K[P[:-1]].T)
+        Qr = Qr * np.sign(np.diag(R))
+        C = (K @ Qr).T
+        rho0 = np.einsum('ab,ab->a', K, K)
+        w = K[P[-1]].copy()
+        for _ in range(2):
+            w -= Qr @ (Qr.T @ w)
+        hist = rho0 - np.vstack((np.zeros(N), np.cumsum(C**2, axis=0)))
+        return dict(crit=rho0 - (C**2).sum(axis=0), Q=Qr, C=C, w=w,
+                    scal=np.array([1.0 / np.linalg.norm(w)])), hist
+    A = K + alpha * np.eye(N)
+    Lc = np.linalg.cholesky(A[np.ix_(P, P)])
+    L = np.linalg.solve(Lc, A[P]).T
+    L1 = L[:, :-1]
+    U = np.ones(N, dtype=bool)
+    U[P[:-1]] = False
+    p = A[:, P[-1]] - L1 @ L1[P[-1]]
+    crit = A[:, U].sum(axis=1) - L1 @ L1[U].sum(axis=0)
+    hist = [A.sum(axis=1)]
+    free = np.ones(N, dtype=bool)
+    for s in range(n - 1):
+        free[P[s]] = False
+        l = L[:, s]
+        hist.append(hist[-1] - l * (l[P[s]] + l[free].sum()))
+    return dict(crit=crit, L=L, p=p), np.array(hist)
+
+
+def restate_state(K, P, method, alpha=0.0):
+    """The recurrences of `_greedy.determinant_host` / `variance_host`, made
+    to pick P."""
+    N, n = len(K), len(P)
+    if method == 'determinant':
+        Q = np.zeros((N, n - 1))
+        C = np.zeros((n - 1, N))
+        rho = np.einsum('ab,ab->a', K, K)
+        hist = [rho.copy()]
+        for s, i in enumerate(P):
+            w = K[i] - Q[:, :s] @ C[:s, i]
+            w2 = w @ w
+            if s + 1 == n:
+                break
+            Q[:, s] = w / np.sqrt(w2)
+            C[s] = K @ Q[:, s]
+            rho = rho - C[s]**2
+            hist.append(rho.copy())
+        return dict(crit=rho, Q=Q, C=C, w=w,
+                    scal=np.array([1.0 / np.sqrt(w2)])), np.array(hist)
+    L = np.zeros((N, n))
+    crit = K.sum(axis=1) + alpha
+    free = np.ones(N, dtype=bool)
+    hist = [crit.copy()]
+    for s, j in enumerate(P):
+        free[j] = False
+        p = K[:, j] - L[:, :s] @ L[j, :s]
+        p[j] += alpha
+        l = p / np.sqrt(p[j])
+        L[:, s] = l
+        if s + 1 == n:
+            break
+        crit = crit - (p + l * l[free].sum())
+        hist.append(crit.copy())
+    return dict(crit=crit, L=L, p=p), np.array(hist)
+
+
+def scales(K, want, method, alpha=0.0):
+    """What an error of each quantity is relative to: the largest |K_a|^2
+    for rho, the largest row sum of |K + alpha I| for the variance criterion,
+    the quantity's own largest entry otherwise."""
+    out = {k: np.abs(v).max() for k, v in want.items() if v.size}
+    if method == 'determinant':
+        out['crit'] = np.einsum('ab,ab->a', K, K).max()
+    else:
+        out['crit'] = np.abs(K + alpha * np.eye(len(K))).sum(axis=1).max()
+    return out
+
+
+def host_error(K, P, method, alpha=0.0):
+    """(definition, its history, scales, E_host): E_host[q] is the largest
+    error of the restated recurrence in quantity q, relative to its scale."""
+    want, hist = define_state(K, P, method, alpha)
+    got, _ = restate_state(K, P, method, alpha)
+    scale = scales(K, want, method, alpha)
+    e_host = {k: np.abs(got[k] - want[k]).max() / scale[k] for k in scale}
+    return want, hist, scale, e_host
+
+
+def bounds(scale, e_host):
+    return {k: FACTOR * max(e_host[k], FLOOR) * scale[k] for k in scale}
+
+
+def history_margins(hist, P):
+    """Along the definition's criterion history, over the samples not chosen
+    before each pick: (the largest best - criterion of the pick, the
+    smallest best - second best)."""
+    free = np.ones(hist.shape[1], dtype=bool)
+    margin, gap = 0.0, np.inf
+    for s, i in enumerate(P):
+        c = hist[s][free]
+        best = c.max()
+        margin = max(margin, best - hist[s][i])
+        if len(c) > 1:
+            gap = min(gap, best - np.partition(c, -2)[-2])
+        free[i] = False
+    return margin, gap
+
+
+@functools.lru_cache(maxsize=None)
+def host_picks(matrix, method, n, alpha=0.0):
+    """The host loop's picks on `matrix` = ('spd', N, seed, dtype) or
+    ('pairs' / 'identity', dtype): computed once for all tests."""
+    from graphdot_amd.model.active_learning import _greedy
+    return tuple(_greedy.run(stored(matrix).astype(np.float64), n, method,
+                             alpha=alpha))
+
+
+def stored(matrix):
+    return spd(*matrix[1:]) if matrix[0] == 'spd' else tie_matrix(*matrix)
+
+
+def alpha_of(matrix, method):
+    """ALPHA for the variance on `spd`; none where the criteria are to stay
+    exactly equal."""
+    return ALPHA if method == 'variance' and matrix[0] == 'spd' else 0.0
+
+
+STATE_MATRICES = \
+    [(('spd', N, 10 + N, dt), n) for N, n in SHAPES + [BEYOND_ONE_CHUNK]
+     for dt in ('float64', 'float32')] + \
+    [((name, dt), 300) for name in ('pairs', 'identity')
+     for dt in ('float64', 'float32')]
+
+
+def matrix_id(case):
+    matrix, n = case
+    return '-'.join(str(x) for x in matrix) + f'-n{n}'
+
+
+@pytest.mark.parametrize('method', ['determinant', 'variance'])
+@pytest.mark.parametrize('case', STATE_MATRICES, ids=matrix_id)
+def test_restated_recurrence_agrees_with_the_definition(case, method):
+    matrix, n = case
+    alpha = alpha_of(matrix, method)
+    K = stored(matrix).astype(np.float64)
+    P = host_picks(matrix, method, n, alpha)
+    assert len(set(P)) == n
+    want, hist, scale, e_host = host_error(K, P, method, alpha)
+    bound = bounds(scale, e_host)['crit']
+    margin, gap = history_margins(hist, P)
+    print(f'{matrix_id(case)} {method}: E_host ' +
+          ' '.join(f'{k} {v:.1e}' for k, v in e_host.items()) +
+          f'; margin {margin / bound:.1e} gap {gap / bound:.1e} of the bound')
+    assert max(e_host.values()) <= E_HOST_CAP, e_host
+    # the picks are the greedy ones of the definition's criteria ...
+    assert margin <= 2 * bound
+    if matrix[0] == 'spd':
+        # ... and on these matrices no rounding within 1000 bounds changes
+        # one: the device has to make the very same picks
+        assert gap > 1000 * bound
+    else:
+        assert gap <= bound             # (ties: the index decides)
+        want =list(range(0, 520, 2)) + list(range(1, 80, 2)) \
+            if matrix[0] == 'pairs' else list(range(300))
+        assert list(P) == want
 
 
 # ---------------------------------------------------------------- the GPU
