@@ -2,8 +2,9 @@
 models that use them): `SourceModule` compiles one HIP source into the JIT
 cache of `jit` and loads it once per process; `STATIC` lists the sources that
 are files of the package, each with its flags, for their host modules and for
-``__graft_entry__.build()``, and `TEXT_UNITS` those that are a device header
-of csrc/device and a few lines of text.  Below them, the few lines every
+``__graft_entry__.build()``, `TEXT_UNITS` those that are a device header of
+csrc/device and a few lines of text, and `FILE_UNITS` those that are the text
+of a header next to its model.  Below them, the few lines every
 torch-facing launch repeats.  Nothing here imports torch (or a package that
 does) at module level: `build()` compiles through this module before
 ``libgdhip.so`` is used.
@@ -130,6 +131,20 @@ TEXT_UNITS = {'knn': SourceModule(source='#include "knn.h"\n\n' + _wrappers(
      'const int64_t *idx, int64_t b, int k, const double *lrd_train, '
      'int64_t n, const double *lrd, double *lof'),
 ))}
+
+
+def _text(relative):
+    with open(os.path.join(_PACKAGE, relative)) as f:
+        return f.read()
+
+
+#: the translation units that are the text of one file of the package which
+#: is no ``.hip`` file, relative to the package
+FILE_UNIT_SOURCES = {'tsne': 'model/manifold/tsne.h'}
+#: name -> SourceModule of that text: an edit of the file changes the key of
+#: its own unit and of no other
+FILE_UNITS = {name: SourceModule(source=_text(p))
+              for name, p in FILE_UNIT_SOURCES.items()}
 
 #: planes / candidates per register chunk (the template parameter KC of the
 #: kernels that keep a chunk of accumulators in registers)

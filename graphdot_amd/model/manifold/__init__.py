@@ -1,0 +1,11 @@
+"""Non-linear maps of graphs on the kernel protocol: exact t-SNE under the
+kernel's feature-space distance, descended on the kernel matrix where it lies
+(the reference has no such model)."""
+try:      # torch's HIP runtime must be initialised before libgdhip's
+    import torch as _torch   # (graphdot_amd.hip.runtime, _let_torch_initialise_first)
+    _torch.cuda.is_available()
+except ImportError:          # pragma: no cover
+    pass
+from .tsne import KernelTSNE
+
+__all__ = ['KernelTSNE']
