@@ -3,8 +3,8 @@ models that use them): `SourceModule` compiles one HIP source into the JIT
 cache of `jit` and loads it once per process; `STATIC` lists the sources that
 are files of the package, each with its flags, for their host modules and for
 ``__graft_entry__.build()``, `TEXT_UNITS` those that are a device header of
-csrc/device and a few lines of text, and `FILE_UNITS` those that are the text
-of a header next to its model.  Below them, the few lines every
+csrc/device and a few lines of text, and `FILE_UNITS` and `MODEL_UNITS` those
+that are the text of a header next to its model.  Below them, the few lines every
 torch-facing launch repeats.  Nothing here imports torch (or a package that
 does) at module level: `build()` compiles through this module before
 ``libgdhip.so`` is used.
@@ -145,6 +145,12 @@ FILE_UNIT_SOURCES = {'tsne': 'model/manifold/tsne.h'}
 #: its own unit and of no other
 FILE_UNITS = {name: SourceModule(source=_text(p))
               for name, p in FILE_UNIT_SOURCES.items()}
+
+#: the same for the models that came after those lists were closed: a new
+#: unit joins this one
+MODEL_UNIT_SOURCES = {'geodesic': 'model/manifold/geodesic.h'}
+MODEL_UNITS = {name: SourceModule(source=_text(p))
+               for name, p in MODEL_UNIT_SOURCES.items()}
 
 #: planes / candidates per register chunk (the template parameter KC of the
 #: kernels that keep a chunk of accumulators in registers)

@@ -8,9 +8,10 @@ try:      # torch's HIP runtime must be initialised before libgdhip's
     _torch.cuda.is_available()
 except ImportError:          # pragma: no cover
     pass
-from .search import KernelNearestNeighbors
+from .search import KernelNearestNeighbors, device_lists
 from .knn import KernelKNeighborsClassifier, KernelKNeighborsRegressor
 from .lof import KernelLocalOutlierFactor
 
 __all__ = ['KernelNearestNeighbors', 'KernelKNeighborsClassifier',
-           'KernelKNeighborsRegressor', 'KernelLocalOutlierFactor']
+           'KernelKNeighborsRegressor', 'KernelLocalOutlierFactor',
+           'device_lists']

@@ -33,6 +33,18 @@ def _count(name, k):
     return int(k)
 
 
+def device_lists(Ks, dq, dt, k, exclude_self=False):
+    """(``(d2 (b, k) float64, idx (b, k) int64, flag (1,) int32)``, fused?)
+    on the device of the (b, n) matrix `Ks`, nothing downloaded: per row the k
+    nearest columns in the order (d2, column), nearest first, with the
+    self-similarities `dq` (b,) and `dt` (n,) float64; `flag` is not zero if
+    some d2 is not finite.  exclude_self: column i is no candidate of row i.
+    The search of the neighbour models, for the models of other packages that
+    build on the lists: the kernels of csrc/device/knn.h where they apply,
+    torch anywhere else."""
+    return _knn.search(Ks, dq, dt, k, exclude_self=exclude_self)
+
+
 class KernelNeighborsBase(KernelMatrices):
     """What the neighbour models share: the training matrix and its diagonal,
     the two searches and the one download of a call."""
