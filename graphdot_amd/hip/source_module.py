@@ -148,7 +148,8 @@ FILE_UNITS = {name: SourceModule(source=_text(p))
 
 #: the same for the models that came after those lists were closed: a new
 #: unit joins this one
-MODEL_UNIT_SOURCES = {'geodesic': 'model/manifold/geodesic.h'}
+MODEL_UNIT_SOURCES = {'geodesic': 'model/manifold/geodesic.h',
+                      'mst': 'model/clustering/mst.h'}
 MODEL_UNITS = {name: SourceModule(source=_text(p))
                for name, p in MODEL_UNIT_SOURCES.items()}
 
